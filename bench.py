@@ -14,14 +14,18 @@ reference), synthetic token data, seq 1024, fixed per-GPU micro-batch (weak scal
 timed step does the full work: forward, backward with overlapped bucketed gradient
 reduce-scatter, fused AdamW on the local shard, parameter all-gather and the cosine LR step.
 K steps are bracketed by barrier + device synchronize on both sides; the slowest rank's time is
-reported.  Rank 0 prints one JSON line (value = whole-job tokens/s).
+reported.  Rank 0 prints one JSON line (value = whole-job tokens/s, ms_per_step = elapsed / K).
 
-"FSDP peak-mem" half of the metric: after the timed throughput phase the ZeRO model is freed
-and a short FSDP (FULL_SHARD, size-based wrap at --numel-to-wrap) phase runs the reference's
-memory-table config (Llama-2-7B, batch 10, seq 1024: /root/reference/04-fully-sharded-data-parallel/
-README.md:271-281) over the same ranks; its per-rank valley (allocated at the end of an
-iteration) and peak (max allocated during it) are reported, max over ranks.  That phase is
-outside the timed region and does not affect `value`.
+A plain run stops there: set-up, W warm-up steps, K timed steps, the line.  `--dump-outputs DIR`
+also writes what the last timed step computed (loss, samples of the updated parameters and of
+the gradients) as DIR/<name>.npy; inputs and initial weights are seeded, so two builds can be
+compared output for output.  Everything else is behind `--full`, after the timed region and
+outside `value`: the reference-timer steps, the replica checksum, the N > 1 sweeps and child
+jobs, and the "FSDP peak-mem" half of the metric -- the ZeRO model is freed and a short FSDP
+(FULL_SHARD, size-based wrap at --numel-to-wrap) phase runs the reference's memory-table config
+(Llama-2-7B, batch 10, seq 1024: the table of its chapter 04 README) over the same ranks; its
+per-rank valley (allocated at the end of an iteration) and peak (max allocated during it) are
+reported, max over ranks.
 """
 from __future__ import annotations
 
@@ -46,6 +50,15 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    # A plain run does what the headline needs: set-up, warm-up, the timed steps, --dump-outputs,
+    # the JSON line.  --full adds every other measurement and check after the timed region (the
+    # reference-timer steps, the FSDP memory phases, the replica checksum and, at N > 1, the
+    # collective and bucket sweeps, the xGMI child job and RCCL's log); their options below
+    # (--ref-steps, --fsdp-mem-*, --coll-sweep-mb, ...) only shape them under --full.
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy "
+                         "(float32): loss, and fixed seeded samples of the updated parameters and of the gradients")
     ap.add_argument("--model", default="llama-3-8b")
     ap.add_argument("--batch-size", type=int, default=16, help="per-GPU micro-batch (sequences)")
     ap.add_argument("--seq-len", type=int, default=1024)
@@ -163,6 +176,41 @@ def loss_in_band(loss: float, vocab: int) -> bool:
     return math.isfinite(loss) and lnv - 3.5 < loss < lnv + 1.5
 
 
+DUMP_SAMPLE = 4 << 20  # elements per sampled array: 16 MiB of float32 each, 32 MiB + the loss in all
+
+
+def _sample_f32(torch, buf, seed):
+    """`buf` flattened as float32 on the host: all of it up to DUMP_SAMPLE elements, else the
+    elements at DUMP_SAMPLE positions drawn once from a generator seeded with `seed` (the same
+    positions in every run of the same job)."""
+    flat = buf.detach().reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(path, torch, engine, loss):
+    """--dump-outputs: what a caller of the timed step holds after its last call -- the loss it
+    returned, the parameters it updated and the gradients it left in this rank's flat buffers
+    (ZeRO / FSDP: this rank's shard of the gradients)."""
+    import numpy as np
+
+    space = getattr(engine, "space", None)
+    if space is not None:
+        if hasattr(engine, "wait_param_gather"):
+            engine.wait_param_gather()
+        params = space.param_buf
+        grads = engine.grad_shard if getattr(engine, "mode", "single") == "zero" else space.grad_buf
+    else:
+        params, grads = engine.shard_params, engine.shard_grads
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    np.save(os.path.join(path, "params.npy"), _sample_f32(torch, params, 4321))
+    np.save(os.path.join(path, "grads.npy"), _sample_f32(torch, grads, 8765))
+
+
 def build_job(args, torch, device, cuda, bucket_mb=None, dp_comm=None):
     """Model + engine + optimizer + scheduler of the flagship step, as the driver's command
     builds them.  `bucket_mb` overrides --bucket-mb (the N > 1 bucket-size sweep)."""
@@ -268,6 +316,8 @@ def throughput_phase(args, torch, dist, device, world, rank, cuda):
     _sync(dist, world, cuda)
     elapsed = time.perf_counter() - t0
     loss_val = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, engine, loss)
     if args.tunableop == "tune" and cuda and rank == 0:
         from dtg.utils.gemm_tuning import save_tunableop
 
@@ -320,7 +370,7 @@ def throughput_phase(args, torch, dist, device, world, rank, cuda):
     res = dict(elapsed=elapsed, peak_gb=peak_gb, loss=loss_val, cfg=cfg, ref_ms=ref_ms,
                mode=getattr(engine, "mode", args.parallel), dp=dp_size, tp_comm=job["tp_comm"],
                dp_comm=getattr(engine, "dp_comm", "rccl"),
-               replica_sum=replica_checksum(engine, torch))
+               replica_sum=replica_checksum(engine, torch) if args.full else float("nan"))
     del model, engine, opt, sched, batches, loss
     close_job(job, torch)
     return res
@@ -597,6 +647,8 @@ def _child_cmd(args, world, what):
            "--sweep-steps", str(args.sweep_steps), "--tunableop", args.tunableop, "--parallel", args.parallel,
            "--tp", str(args.tp), "--tp-overlap-chunks", str(args.tp_overlap_chunks),
            "--dp-comm", args.dp_comm, "--tp-comm", args.tp_comm]
+    if args.full:
+        cmd += ["--full"]
     if args.backend:
         cmd += ["--backend", args.backend]
     return cmd
@@ -770,6 +822,9 @@ def _load_rccl_module():
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
+    if not args.full and not args.diag_only:  # a plain run: the headline alone (see --full)
+        args.ref_steps = args.fsdp_mem_steps = args.xgmi_child = 0
+        args.coll_sweep_mb = args.bucket_sweep_mb = ""
     # DTG_FAKE_WORLD=N: rehearsal of rank 0 of an N-rank job on one GPU; the other ranks are
     # PyTorch's fake process group (collectives return at once).  Shapes, shard layouts, kernels
     # and memory are those of the real N-rank job; the time excludes communication and is labelled.
@@ -788,7 +843,8 @@ def main(argv=None):
     if multi and args.rccl_preset != "none":
         _rccl = _load_rccl_module()  # stdlib-only: importing it does not touch the GPU
         rccl_applied = _rccl.apply_preset(args.rccl_preset)
-        rccl_log = _rccl.arm_log(f"rank{os.environ.get('RANK', '0')}_{os.getpid()}")
+        if args.full:
+            rccl_log = _rccl.arm_log(f"rank{os.environ.get('RANK', '0')}_{os.getpid()}")
 
     import gc
 
@@ -934,7 +990,7 @@ def main(argv=None):
                     rec[f"{k}_comm_calibration"] = calib[k]
             if "error" in calib:
                 rec["transport_calibration_error"] = calib
-        if multi and backend == "nccl":
+        if multi and backend == "nccl" and args.full:
             rec["rccl"] = _load_rccl_module().diagnose(rccl_log)
             rec["rccl"]["preset_applied"] = rccl_applied
     reporter.rec = rec

@@ -16,6 +16,8 @@ ARGS = ["--steps", "2", "--warmup", "1", "--model", "llama-tiny", "--batch-size"
         "--tunableop", "off", "--fsdp-mem-model", "llama-tiny", "--fsdp-mem-batch", "2", "--fsdp-mem-seq", "64",
         "--fsdp-mem-steps", "1", "--numel-to-wrap", "10000", "--coll-sweep-mb", "1,2",
         "--bucket-sweep-mb", "1,4", "--sweep-steps", "1", "--ref-steps", "2"]
+PLAIN = list(ARGS)  # a plain run: the headline alone, whatever the diagnostics' options say
+ARGS = ARGS + ["--full"]  # every diagnostic after the timed region
 
 
 def _json_lines(out):
@@ -58,6 +60,60 @@ def test_bench_single_process():
     recs = _json_lines(r.stdout)
     assert len(recs) == 1
     _check(recs[0], 1)
+
+
+def _plain(tmp_path, name):
+    out = tmp_path / name
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", str(out)]
+                       + PLAIN, capture_output=True, text=True, timeout=300, env=dict(os.environ, OMP_NUM_THREADS="2"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    recs = _json_lines(r.stdout)
+    assert len(recs) == 1
+    return recs[0], out, r.stderr
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full nothing runs after the timed steps (no reference-timer steps, no FSDP
+    memory phase, even with their options given); the headline fields keep their meaning;
+    --steps is the number of timed steps; --dump-outputs writes the last timed step's loss,
+    updated parameters and gradients as float32 .npy, identical from run to run."""
+    import numpy as np
+
+    rec, out, err = _plain(tmp_path, "a")
+    assert rec["metric"].startswith("tokens/sec/GPU") and rec["unit"] == "tokens/s (whole job)"
+    assert rec["higher_is_better"] is True and rec["dtype"] == "bf16"
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - 2 * 64 * 2 / (rec["ms_per_step"] * 2 / 1000)) < 0.02 * rec["value"]
+    for k in ("fsdp_mem", "fsdp_peak_mem_gb", "fsdp_mem_one_rank_of_w", "tok_s_reference_timers", "reference_timer_ms",
+              "collectives", "bucket_sweep", "xgmi_diag", "diagnostic_errors"):
+        assert k not in rec, k
+    assert set(rec["phase_s"]) == {"startup_and_calibration", "throughput"}
+    assert err.count("warmup step") == 1
+    a = {n: np.load(out / f"{n}.npy") for n in ("loss", "params", "grads")}
+    assert sorted(p.name for p in out.iterdir()) == ["grads.npy", "loss.npy", "params.npy"]
+    assert all(v.dtype == np.float32 and v.ndim == 1 and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["loss"].shape == (1,) and abs(float(a["loss"][0]) - rec["final_loss"]) < 1e-3
+    # llama-tiny is smaller than the sample size: the whole flat buffers, one gradient per parameter
+    assert a["params"].size == a["grads"].size > 0 and np.abs(a["grads"]).max() > 0
+    rec2, out2, _ = _plain(tmp_path, "b")
+    for n, v in a.items():
+        assert np.array_equal(v, np.load(out2 / f"{n}.npy")), n
+
+
+def test_bench_dump_samples_large_buffers_at_fixed_positions():
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    big = torch.arange(bench.DUMP_SAMPLE + 1000, dtype=torch.float32)
+    s1, s2 = bench._sample_f32(torch, big, 5), bench._sample_f32(torch, big.clone(), 5)
+    assert s1.dtype == np.float32 and s1.size == bench.DUMP_SAMPLE and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) >= 0) and s1.max() > bench.DUMP_SAMPLE  # positions over the whole buffer
+    small = torch.arange(10, dtype=torch.bfloat16)
+    assert np.array_equal(bench._sample_f32(torch, small, 5), np.arange(10, dtype=np.float32))
 
 
 @pytest.mark.slow

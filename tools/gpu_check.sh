@@ -22,7 +22,7 @@ timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$out/
     || { tail -20 "$out/smoke.log"; exit 1; }
 tail -1 "$out/smoke.log"
 echo "[gpu_check] bench"
-timeout -k 10 300 python -u bench.py > "$out/bench.log" 2>&1 || { tail -20 "$out/bench.log"; exit 1; }
+timeout -k 10 300 python -u bench.py --full > "$out/bench.log" 2>&1 || { tail -20 "$out/bench.log"; exit 1; }
 tail -1 "$out/bench.log"
 if [ "${PROFILE:-1}" = "1" ]; then
   echo "[gpu_check] rocprofv3 kernel stats"

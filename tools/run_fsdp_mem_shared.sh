@@ -15,7 +15,7 @@ trap "kill $HB" EXIT
 DTG_SHARED_DEVICE=1 timeout -k 10 ${LIMIT:-900} python -u -m torch.distributed.run --nnodes 1 --nproc-per-node $W \
     --master-addr 127.0.0.1 --master-port 29575 bench.py --gpus $W --backend gloo \
     --model llama-tiny --batch-size 2 --seq-len 256 --steps 2 --warmup 1 --coll-sweep-mb "" \
-    --fsdp-mem-steps ${FSDP_STEPS:-3} > "$OUT/fsdp_mem_w$W.log" 2>&1
+    --full --fsdp-mem-steps ${FSDP_STEPS:-3} >"$OUT/fsdp_mem_w$W.log" 2>&1
 rc=$?
 echo "fsdp_mem W=$W rc=$rc"
 tail -1 "$OUT/fsdp_mem_w$W.log" | grep -o '"fsdp_mem.*' || tail -30 "$OUT/fsdp_mem_w$W.log"
