@@ -69,16 +69,20 @@ __device__ __forceinline__ void adam_elem(float& pv, float gv, float& mv, float&
 // `dev_hyper` (optional, f32 [3] = lr, 1 - beta1^t, sqrt(1 - beta2^t)) overrides the launch
 // arguments: a HIP-graph-captured step replays the same kernel arguments every time, so the
 // step-dependent values live in device memory the host rewrites before each replay.
+// `gscale` (optional, device f32 [1]) multiplies grad_scale: the gradient-clipping coefficient,
+// computed on the device from the global gradient norm (grad_norm.hip), with no host sync.
 template <typename GT, typename ST, bool MASTER, bool VEC, int U = 2>
 __global__ __launch_bounds__(256) void adamw_kernel(uint16_t* __restrict__ p, float* __restrict__ master,
                                                     const GT* __restrict__ g, ST* __restrict__ m,
                                                     ST* __restrict__ v, int64_t n, AdamHyper h,
-                                                    const float* __restrict__ dev_hyper) {
+                                                    const float* __restrict__ dev_hyper,
+                                                    const float* __restrict__ gscale) {
   if (dev_hyper != nullptr) {
     h.lr = dev_hyper[0];
     h.bc1 = dev_hyper[1];
     h.bc2_sqrt = dev_hyper[2];
   }
+  if (gscale != nullptr) h.grad_scale *= gscale[0];
   const float step_size = h.lr / h.bc1;
   const float decay = 1.f - h.lr * h.wd;
   if constexpr (VEC) {
@@ -136,9 +140,18 @@ __global__ __launch_bounds__(256) void adamw_kernel(uint16_t* __restrict__ p, fl
   }
 }
 
+// The optional device-side gradient scale of adamw_ / adamw_t_: f32 [1] on p's device.
+static const float* gscale_ptr(const c10::optional<at::Tensor>& gscale, const at::Tensor& p, const char* op) {
+  if (!gscale.has_value() || !gscale->defined()) return nullptr;
+  DTG_CHECK(gscale->is_cuda() && gscale->device() == p.device() && gscale->scalar_type() == at::kFloat &&
+                gscale->numel() >= 1 && gscale->is_contiguous(), op, ": gscale must be a contiguous f32 GPU tensor");
+  return gscale->data_ptr<float>();
+}
+
 void adamw_(const at::Tensor& p, const c10::optional<at::Tensor>& master, const at::Tensor& g,
             const at::Tensor& m, const at::Tensor& v, double lr, double beta1, double beta2,
-            double eps, double wd, int64_t step, double grad_scale, const c10::optional<at::Tensor>& hyper) {
+            double eps, double wd, int64_t step, double grad_scale, const c10::optional<at::Tensor>& hyper,
+            const c10::optional<at::Tensor>& gscale) {
   DTG_CHECK_CUDA_BF16(p);
   DTG_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(),
             "adamw_: buffers must be contiguous");
@@ -153,6 +166,7 @@ void adamw_(const at::Tensor& p, const c10::optional<at::Tensor>& master, const 
               "adamw_: hyper must be a contiguous f32 GPU tensor [lr, 1-beta1^t, sqrt(1-beta2^t)]");
     hp = hyper->data_ptr<float>();
   }
+  const float* gsp = gscale_ptr(gscale, p, "adamw_");
   if (has_master)
     DTG_CHECK(master->scalar_type() == at::kFloat && master->numel() == n && master->is_contiguous(),
               "adamw_: master must be contiguous f32");
@@ -185,10 +199,10 @@ void adamw_(const at::Tensor& p, const c10::optional<at::Tensor>& master, const 
 #define DTG_ADAM_LAUNCH(GT, ST, MASTER)                                                      \
   do { if (vec) adamw_kernel<GT, ST, MASTER, true, unroll><<<blocks, threads, 0, stream()>>>(       \
       bf16_mut(p), mp, reinterpret_cast<const GT*>(g.data_ptr()), reinterpret_cast<ST*>(m.data_ptr()), \
-      reinterpret_cast<ST*>(v.data_ptr()), n, h, hp);                                       \
+      reinterpret_cast<ST*>(v.data_ptr()), n, h, hp, gsp);                                       \
   else adamw_kernel<GT, ST, MASTER, false><<<blocks, threads, 0, stream()>>>(               \
       bf16_mut(p), mp, reinterpret_cast<const GT*>(g.data_ptr()), reinterpret_cast<ST*>(m.data_ptr()), \
-      reinterpret_cast<ST*>(v.data_ptr()), n, h, hp); } while (0)
+      reinterpret_cast<ST*>(v.data_ptr()), n, h, hp, gsp); } while (0)
   if (has_master) {
     if (gb && sb) DTG_ADAM_LAUNCH(uint16_t, uint16_t, true);
     else if (gb) DTG_ADAM_LAUNCH(uint16_t, float, true);
@@ -254,12 +268,14 @@ __global__ __launch_bounds__(TC) void adamw_t_reg_kernel(uint16_t* __restrict__ 
                                                          const uint16_t* __restrict__ g, ST* __restrict__ m,
                                                          ST* __restrict__ v, uint16_t* __restrict__ pt,
                                                          const MatDesc* __restrict__ mats, int nmats, AdamHyper h,
-                                                         const float* __restrict__ dev_hyper) {
+                                                         const float* __restrict__ dev_hyper,
+                                                         const float* __restrict__ gscale) {
   if (dev_hyper != nullptr) {
     h.lr = dev_hyper[0];
     h.bc1 = dev_hyper[1];
     h.bc2_sqrt = dev_hyper[2];
   }
+  if (gscale != nullptr) h.grad_scale *= gscale[0];
   const float step_size = h.lr / h.bc1;
   const float decay = 1.f - h.lr * h.wd;
   const int64_t t = blockIdx.x;
@@ -321,7 +337,7 @@ __global__ __launch_bounds__(TC) void adamw_t_reg_kernel(uint16_t* __restrict__ 
 void adamw_t_(const at::Tensor& p, const c10::optional<at::Tensor>& master, const at::Tensor& g, const at::Tensor& m,
               const at::Tensor& v, const at::Tensor& pt, const at::Tensor& mats, int64_t ntiles, double lr,
               double beta1, double beta2, double eps, double wd, int64_t step, double grad_scale,
-              const c10::optional<at::Tensor>& hyper, int64_t tile_cols) {
+              const c10::optional<at::Tensor>& hyper, int64_t tile_cols, const c10::optional<at::Tensor>& gscale) {
   DTG_CHECK_CUDA_BF16(p);
   DTG_CHECK_CUDA_BF16(pt);
   DTG_CHECK(g.scalar_type() == at::kBFloat16, "adamw_t_: grads must be bf16");
@@ -346,6 +362,7 @@ void adamw_t_(const at::Tensor& p, const c10::optional<at::Tensor>& master, cons
               "adamw_t_: hyper must be a contiguous f32 GPU tensor");
     hp = hyper->data_ptr<float>();
   }
+  const float* gsp = gscale_ptr(gscale, p, "adamw_t_");
   const int nm = (int)mats.size(0);
   if (nm == 0 || ntiles == 0) return;
   const c10::DeviceGuard gd(p.device());
@@ -368,7 +385,7 @@ void adamw_t_(const at::Tensor& p, const c10::optional<at::Tensor>& master, cons
 #define DTG_ADAMT_REG(ST, MASTER, TC)                                                                       \
   adamw_t_reg_kernel<ST, MASTER, TC><<<(unsigned)ntiles, TC, 0, stream()>>>(                                \
       bf16_mut(p), mp, gp, reinterpret_cast<ST*>(m.data_ptr()), reinterpret_cast<ST*>(v.data_ptr()), ptp, md, nm, \
-      h, hp)
+      h, hp, gsp)
 #define DTG_ADAMT_REG_TC(ST, MASTER)                                 \
   do {                                                                \
     if (tile_cols == 64) DTG_ADAMT_REG(ST, MASTER, 64);               \

@@ -110,23 +110,25 @@ def ce_grad_(logits, labels, lse, vocab_start, ignore_index, grad_scale):
 
 
 def adamw_t_(p, master, g, m, v, pt, mats, ntiles, lr, beta1, beta2, eps, wd, step, grad_scale, hyper=None,
-             tile_cols=64):
+             tile_cols=64, gscale=None):
     """The HIP kernel's semantics: only the elements of the listed matrices are updated; each
     matrix with a transposed slot gets its new values transposed into `pt`."""
     for off, rows, cols, toff, _ in mats.tolist():
         n = rows * cols
         sl = slice(off, off + n)
         adamw_(p[sl], None if master is None else master[sl], g[sl], m[sl], v[sl], lr, beta1, beta2, eps, wd,
-               step, grad_scale, hyper)
+               step, grad_scale, hyper, gscale)
         if toff >= 0:
             pt[toff:toff + n].copy_(p[sl].view(rows, cols).t().reshape(-1))
 
 
-def adamw_(p, master, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale, hyper=None):
+def adamw_(p, master, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale, hyper=None, gscale=None):
     bc1 = 1 - beta1**step
     bc2 = math.sqrt(1 - beta2**step)
     if hyper is not None:
         lr, bc1, bc2 = (float(x) for x in hyper[:3].tolist())
+    if gscale is not None:  # the kernel's f32 product grad_scale * gscale[0]
+        grad_scale = float(torch.tensor(grad_scale, dtype=torch.float32) * gscale.float().reshape(-1)[0])
     pf = master if master is not None else p.float()
     gf = g.float() * grad_scale
     mf, vf = m.float(), v.float()
@@ -139,6 +141,16 @@ def adamw_(p, master, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale, hype
     if master is not None:
         master.copy_(pf)
     p.copy_(pf)
+
+
+_SUMSQ_CHUNK = 1 << 20
+
+
+def grad_sumsq_(g, acc, slot):
+    """acc[slot] += sum(g^2) in f32, a chunk at a time (no f32 temporary the size of g)."""
+    assert g.dim() == 1 and acc.dtype == torch.float32
+    for i in range(0, g.numel(), _SUMSQ_CHUNK):
+        acc[slot] += g[i:i + _SUMSQ_CHUNK].float().square().sum()  # not in place: .float() of f32 is g itself
 
 
 def _key_ranges(cu_seqlens, k_start=None, k_len=None):
@@ -453,7 +465,7 @@ def flash_attn_tuning(like, kv_split, kv_qb):
 for _name, _fn in list(globals().items()):
     if _name in (
         "rmsnorm_fwd", "add_rmsnorm_fwd", "rmsnorm_bwd", "rope_", "swiglu_fwd", "swiglu_bwd",
-        "ce_fwd_bwd_", "ce_stats", "ce_grad_", "adamw_", "adamw_t_", "flash_attn_fwd", "flash_attn_bwd",
+        "ce_fwd_bwd_", "ce_stats", "ce_grad_", "adamw_", "adamw_t_", "grad_sumsq_", "flash_attn_fwd", "flash_attn_bwd",
         "flash_attn_bwd_qkv", "transpose2d", "transpose_mats_", "swiglu_bwd_t", "embedding_bwd_", "flash_attn_varlen_fwd",
         "flash_attn_varlen_bwd", "flash_attn_fwd_drop", "flash_attn_bwd_drop", "flash_attn_bwd_qkv_drop", "philox_rng",
         "flash_attn_bwd_qkv_rope", "flash_attn_tuning",

@@ -21,13 +21,17 @@ _DEFS = [
     "ce_stats(Tensor logits, Tensor labels, int vocab_start) -> (Tensor, Tensor, Tensor)",
     "ce_grad_(Tensor(a!) logits, Tensor labels, Tensor lse, int vocab_start, int ignore_index, float grad_scale) -> ()",
     "adamw_(Tensor(a!) p, Tensor(b!)? master, Tensor g, Tensor(c!) m, Tensor(d!) v, float lr, float beta1, "
-    "float beta2, float eps, float wd, int step, float grad_scale, Tensor? hyper=None) -> ()",
+    "float beta2, float eps, float wd, int step, float grad_scale, Tensor? hyper=None, Tensor? gscale=None) -> ()",
     # AdamW over the matrices `mats` (int64 [n, 5]: offset, rows, cols, transposed offset or -1,
     # first tile, counted in 64 x tile_cols tiles) of the flat buffers, also writing each matrix's
     # transpose into `pt`
     "adamw_t_(Tensor(a!) p, Tensor(b!)? master, Tensor g, Tensor(c!) m, Tensor(d!) v, Tensor(e!) pt, Tensor mats, "
     "int ntiles, float lr, float beta1, float beta2, float eps, float wd, int step, float grad_scale, "
-    "Tensor? hyper=None, int tile_cols=64) -> ()",
+    "Tensor? hyper=None, int tile_cols=64, Tensor? gscale=None) -> ()",
+    # acc[slot] += sum of squares of the contiguous 1-D gradient buffer g (bf16 / f32), accumulated
+    # in f32, bitwise reproducible; `gscale` of adamw_ / adamw_t_ above is the device f32 [1] clip
+    # coefficient derived from it, multiplied into grad_scale by the kernel
+    "grad_sumsq_(Tensor g, Tensor(a!) acc, int slot) -> ()",
     "adamw_cpu_(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, float lr, float beta1, float beta2, "
     "float eps, float wd, int step, float grad_scale) -> ()",
     # window > 0 (causal only): sliding window, query i sees keys (i - window, i]

@@ -57,12 +57,20 @@ class DataParallel:
                  bucket_mb: int = 256, broadcast_from_rank0: bool = True, state_dtype=torch.bfloat16,
                  master_weights: bool = False, overlap_param_gather: bool = True,
                  overlap_optimizer: bool = False, grad_divisor: Optional[int] = None,
-                 force_collectives: bool = False, weight_t: Optional[bool] = None, dp_comm: str = "rccl"):
-        """dp_comm: "rccl" (default; also the inter-node path) or "xgmi-dma": ZeRO's gradient
+                 force_collectives: bool = False, weight_t: Optional[bool] = None, dp_comm: str = "rccl",
+                 max_grad_norm: Optional[float] = None):
+        """max_grad_norm: clip the averaged gradient to this global L2 norm before the update
+        (None = off, nothing new runs; float("inf") = only measure).  After a step `last_grad_norm`
+        and `last_clip_coef` are device scalars (not synced).  See parallel/grad_clip.py.
+
+        dp_comm: "rccl" (default; also the inter-node path) or "xgmi-dma": ZeRO's gradient
         reduce-scatter and parameter all-gather as copy-engine pulls between the ranks' shared
         flat buffers over xGMI (parallel/xgmi_dp.py; one node, no CU time in the overlap)."""
         assert mode in ("single", "ddp", "zero")
         assert dp_comm in ("rccl", "xgmi-dma"), dp_comm
+        if max_grad_norm is not None and overlap_optimizer:
+            raise ValueError("max_grad_norm cannot be combined with overlap_optimizer=True: the global gradient "
+                             "norm needs every gradient before the first bucket is updated")
         self.module = model
         self.group = group
         self.tp_group = tp_group
@@ -114,6 +122,16 @@ class DataParallel:
         if master_weights:
             self.master = torch.empty(self.shard_numel, dtype=torch.float32, device=dev)
             self._shard_param_copy(self.master)
+        # global-norm clipping / grad-norm measurement (None: off, the step is exactly as without it)
+        self.clip = None
+        self.last_grad_norm = self.last_clip_coef = None
+        if max_grad_norm is not None:
+            from .grad_clip import GradClip
+
+            self.clip = GradClip(max_grad_norm, dev, shard_group=group, sharded=self.mode == "zero",
+                                 tp_group=tp_group)
+            if self.xdp is not None:  # IPC-shared buffers are not zero-filled: the norm reads the padding
+                self.space.grad_buf.zero_()
         self.step_count = 0
         self.accum_count = 0  # micro-batches accumulated since the last step
         # ZeRO: the post-step parameter all-gathers are left in flight and each bucket is waited
@@ -402,6 +420,18 @@ class DataParallel:
         else:
             out.copy_(self.space.param_buf)
 
+    def _grad_pieces(self):
+        """(view, slot) pieces of this rank's final gradient for the global norm: slot 1 = the
+        trailing bucket of TP-replicated parameters (counted once over TP), slot 0 = the rest.
+        single / ddp: the whole (already identical) gradient buffer; zero: this rank's shard.
+        The flat buffers' padding is never written and stays zero, so it adds nothing."""
+        sp = self._sp_bucket
+        if self.mode == "zero":
+            cut = self.shard_offsets[sp.index] if sp is not None else self.shard_numel
+            return [(self.grad_shard[:cut], 0), (self.grad_shard[cut:], 1)]
+        cut = sp.start if sp is not None else self.space.numel
+        return [(self.space.grad_buf[:cut], 0), (self.space.grad_buf[cut:], 1)]
+
     def step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=None):
         if self._bwd_stepped:  # overlap_optimizer: every bucket was updated during backward
             assert all(b.stepped for b in self.space.buckets), "a bucket missed its in-backward update"
@@ -412,6 +442,10 @@ class DataParallel:
         self.step_count += 1
         if grad_scale is None:
             grad_scale = 1.0 / (self.grad_divisor * max(1, self.accum_count))
+        gscale = None
+        if self.clip is not None:  # the norm of the averaged gradient: pre_scale = AdamW's grad_scale
+            gscale = self.clip.update(self._grad_pieces(), grad_scale)
+            self.last_grad_norm, self.last_clip_coef = self.clip.norm, self.clip.coef
         if self.mode == "zero":
             self.wait_param_gather()  # never update a slice an all-gather may still be reading
             if self._wt_stream is not None:  # ... or a W^T transpose
@@ -421,7 +455,8 @@ class DataParallel:
                 adamw_step(self.space.param_buf[s:e], self.grad_shard[o:o + n], self.exp_avg[o:o + n],
                            self.exp_avg_sq[o:o + n], lr=lr, step=self.step_count, beta1=beta1, beta2=beta2,
                            eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
-                           master=None if self.master is None else self.master[o:o + n], hyper=self.graph_hyper)
+                           master=None if self.master is None else self.master[o:o + n], hyper=self.graph_hyper,
+                           gscale=gscale)
             if self._wt_buf is not None:
                 self._wt_version = self.space.param_buf._version
                 for b in self._wt_valid:
@@ -431,12 +466,12 @@ class DataParallel:
             torch.ops.dtg.adamw_t_(self.space.param_buf, self.master, self.space.grad_buf, self.exp_avg,
                                    self.exp_avg_sq, self._wt_buf, self._wt_mats, int(self._wt_tiles), float(lr),
                                    float(beta1), float(beta2), float(eps), float(weight_decay), int(self.step_count),
-                                   float(grad_scale), self.graph_hyper, self._wt_tc)
+                                   float(grad_scale), self.graph_hyper, self._wt_tc, gscale)
             self._wt_version = self.space.param_buf._version
         else:
             adamw_step(self.space.param_buf, self.space.grad_buf, self.exp_avg, self.exp_avg_sq, lr=lr,
                        step=self.step_count, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
-                       grad_scale=grad_scale, master=self.master, hyper=self.graph_hyper)
+                       grad_scale=grad_scale, master=self.master, hyper=self.graph_hyper, gscale=gscale)
 
     def _allgather_params(self, wait: bool = True):
         """ZeRO: every rank updated its slice of each bucket; all-gather them in place, in the

@@ -135,7 +135,14 @@ class FullyShard:
                  state_dtype=torch.bfloat16, init_fn: Optional[Callable] = None, seed: int = 0,
                  prefetch: bool = True, max_inflight_rs: int = 2, tp_group=None, replicate_group=None,
                  overlap_cpu_step: bool = True, force_collectives: bool = False, offload_params: bool = True,
-                 grad_ring: int = 0, dp_comm: str = "rccl"):
+                 grad_ring: int = 0, dp_comm: str = "rccl", max_grad_norm: Optional[float] = None):
+        """max_grad_norm: clip the averaged gradient to this global L2 norm before the update
+        (None = off; float("inf") = only measure); `last_grad_norm` / `last_clip_coef` are device
+        scalars after a step (parallel/grad_clip.py).  GPU-resident state only."""
+        if max_grad_norm is not None and cpu_offload:
+            raise NotImplementedError("max_grad_norm is not supported with cpu_offload=True yet: the gradient shards "
+                                      "live in host memory (and are updated during backward), and the host-side "
+                                      "sum of squares is not implemented")
         self.module = model
         self.group = group
         # HYBRID_SHARD (ZeRO++-style): shard inside `group` (one node's xGMI island), replicate
@@ -307,6 +314,14 @@ class FullyShard:
         model.register_forward_pre_hook(self._root_pre_forward)
         if self.root is not None:
             model.register_forward_hook(self._root_post_forward)
+        self.clip = None
+        self.last_grad_norm = self.last_clip_coef = None
+        if max_grad_norm is not None:
+            from .grad_clip import GradClip
+
+            self.clip = GradClip(max_grad_norm, self.device, shard_group=group, sharded=self._coll,
+                                 tp_group=tp_group)
+            self._clip_pieces = self._grad_pieces()
         self._rs_inflight = deque()
         self._order: List[_Unit] = []  # forward execution order (recorded on the first step)
         self._record_order = True
@@ -680,6 +695,27 @@ class FullyShard:
         self._first_micro = True
 
     # ------------------------------------------------------------------ optimizer
+    def _grad_pieces(self):
+        """(view of shard_grads, slot) for the global gradient norm: the parts of this rank's shard
+        that hold parameters (the padding between them is never written), slot 1 for each unit's
+        TP-replicated tail (counted once over TP), slot 0 for the rest.  Neighbouring ranges of one
+        slot are merged: one per unit and slot when every parameter is a multiple of 16 elements."""
+        tp_on = self.tp_group is not None and comm.world(self.tp_group) > 1
+        ranges = []
+        for u in self.all_units:
+            s, e = self.rank * u.shard_numel, (self.rank + 1) * u.shard_numel
+            for i, shape in enumerate(u.shapes):
+                lo, hi = max(u.offsets[i], s), min(u.offsets[i] + math.prod(shape), e)
+                if lo >= hi:
+                    continue
+                slot = 1 if (tp_on and i >= len(u.shapes) - u.n_sp) else 0
+                lo, hi = u.shard_off + lo - s, u.shard_off + hi - s
+                if ranges and ranges[-1][2] == slot and ranges[-1][1] == lo:
+                    ranges[-1][1] = hi
+                else:
+                    ranges.append([lo, hi, slot])
+        return [(self.shard_grads[lo:hi], slot) for lo, hi, slot in ranges]
+
     def step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=None):
         if self._poisoned:
             raise RuntimeError("FullyShard.step: a failed backward left units partially updated")
@@ -713,8 +749,13 @@ class FullyShard:
             if self.resident:
                 self.sync_params_after_load()
         else:
+            gscale = None
+            if self.clip is not None:  # HYBRID: the shards are already summed over the replicas
+                gscale = self.clip.update(self._clip_pieces, grad_scale)
+                self.last_grad_norm, self.last_clip_coef = self.clip.norm, self.clip.coef
             adamw_step(self.shard_params, self.shard_grads, self.exp_avg, self.exp_avg_sq, lr=lr, step=self.step_count,
-                       beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+                       beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
+                       gscale=gscale)
 
     def _xfer_add(self, kind, t0, t1, nbytes):
         xs = self._xfer[kind]

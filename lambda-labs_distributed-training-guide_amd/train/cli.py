@@ -106,6 +106,13 @@ def get_parser(chapter: str) -> argparse.ArgumentParser:
         g.add_argument("--pp-microbatches", default=4, type=int,
                        help="1F1B micro-batches per step (must divide --batch-size)")
     g.add_argument("--grad-accum", default=1, type=int, help="micro-batches per optimizer step (no_sync)")
+    g.add_argument("--max-grad-norm", default=0.0, type=float,
+                   help="clip the (averaged) gradient to this global L2 norm before every update, as "
+                        "torch.nn.utils.clip_grad_norm_ does; computed on the device, no host sync (0 = off).  "
+                        "Not with --pp > 1 or --cpu-offload on")
+    g.add_argument("--log-grad-norm", default="off", choices=["on", "off"],
+                   help="add grad_norm (and grad_clip_coef when clipping) to the metric record; on without "
+                        "--max-grad-norm only measures the norm")
     g.add_argument("--detect-anomaly", default="off", choices=["on", "off"],
                    help="debugging: torch.autograd anomaly mode (raises at the first backward op whose output "
                         "is NaN, with the forward stack that created it); slow")

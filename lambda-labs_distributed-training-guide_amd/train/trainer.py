@@ -63,7 +63,30 @@ def _deepspeed_overrides(args):
     # ZeRO-Offload (optimizer only) keeps parameters on the device; offload_param moves them too
     args.offload_params = "on" if (zero.get("offload_param") or {}).get("device", "none") == "cpu" else "off"
     args.grad_accum = int(cfg.get("gradient_accumulation_steps", args.grad_accum))
+    clip = float(cfg.get("gradient_clipping", 0) or 0)
+    if clip > 0:  # DeepSpeed's global-norm clipping; an explicit --max-grad-norm wins
+        args.max_grad_norm = args.max_grad_norm if args.max_grad_norm > 0 else clip
     return args
+
+
+def _max_grad_norm(args, chapter):
+    """--max-grad-norm / --log-grad-norm -> the engines' max_grad_norm (None: off; inf: measure
+    only).  Unsupported combinations end the run here, before any model is built."""
+    clip = float(getattr(args, "max_grad_norm", 0.0) or 0.0)
+    if clip < 0 or clip != clip:
+        raise SystemExit(f"--max-grad-norm must be >= 0 (0 = off), got {clip}")
+    log = getattr(args, "log_grad_norm", "off") == "on"
+    if clip == 0 and not log:
+        return None
+    what = "--max-grad-norm" if clip > 0 else "--log-grad-norm on"
+    if max(1, getattr(args, "pp", 1)) > 1:
+        raise SystemExit(f"{what} is not supported with --pp > 1: the stages hold disjoint parameters and the "
+                         "norm is not reduced over the pipeline group yet")
+    fsdp = chapter in ("04", "05", "07") or (chapter == "deepspeed" and getattr(args, "zero_stage", 3) == 3)
+    if fsdp and getattr(args, "cpu_offload", "off") == "on":
+        raise SystemExit(f"{what} is not supported with --cpu-offload on yet: the gradient shards live in host "
+                         "memory and the host-side sum of squares is not implemented")
+    return clip if clip > 0 else float("inf")
 
 
 def _offload_params(args, model, dp_group, device) -> bool:
@@ -166,6 +189,7 @@ def _resolve_dp_comm(args, chapter, cfg, device, dp_group, world, fsdp, pp, nseq
 
 def _build(args, chapter, device, world):
     """Model + engine + optimizer for a chapter.  Returns (model, engine, dp_size, dp_rank, ckpt_style)."""
+    max_grad_norm = _max_grad_norm(args, chapter)
     depth = getattr(args, "num_layers", None)
     cfg = resolve_config(args.model_name, **({} if depth is None else {"num_hidden_layers": depth}))
     if chapter == "rime" and cfg.vocab_size != 156939:
@@ -284,7 +308,7 @@ def _build(args, chapter, device, world):
                             min_num_params=getattr(args, "numel_to_wrap", 100_000_000), device=device,
                             reshard_after_forward=args.reshard_after_forward == "on",
                             cpu_offload=cpu_offload, offload_params=offload_params, seed=args.seed,
-                            replicate_group=replicate_group, grad_ring=ring,
+                            replicate_group=replicate_group, grad_ring=ring, max_grad_norm=max_grad_norm,
                             dp_comm=getattr(args, "dp_comm", "rccl") if device.type == "cuda" else "rccl")
         if getattr(engine, "xdp", None) is not None:
             LOGGER.info("FSDP collectives: copy-engine pulls over xGMI (shared shard buffers, gradient pool)")
@@ -308,6 +332,7 @@ def _build(args, chapter, device, world):
                               tp_group=tp_group,
                               bucket_mb=args.bucket_mb, broadcast_from_rank0=tp_group is None,
                               grad_divisor=dp_size if seq is not None else None,
+                              max_grad_norm=max_grad_norm,
                               dp_comm=getattr(args, "dp_comm", "rccl") if device.type == "cuda" else "rccl")
         if getattr(engine, "xdp", None) is not None:
             LOGGER.info("ZeRO collectives: copy-engine pulls over xGMI between the ranks' shared flat buffers")
@@ -332,6 +357,7 @@ def run(chapter: str, argv=None):
     args = parser.parse_args(argv)
     if chapter == "deepspeed":
         args = _deepspeed_overrides(args)
+    _max_grad_norm(args, chapter)  # unsupported combinations end the run before anything is built
     rank, local_rank, world, device = udist.init_distributed(local_rank_arg=getattr(args, "local_rank", None))
     if getattr(args, "detect_anomaly", "off") == "on":
         torch.autograd.set_detect_anomaly(True, check_nan=True)
@@ -545,6 +571,11 @@ def run(chapter: str, argv=None):
                     info.update(_offload_info(engine))
                 if args.activation_checkpointing == "on":
                     info["ac/layers"] = checkpointed_count(model)
+                if getattr(engine, "last_grad_norm", None) is not None:
+                    # the last step's values; the loop has just synced for running_loss
+                    info["grad_norm"] = float(engine.last_grad_norm)
+                    if not engine.clip.measure_only:
+                        info["grad_clip_coef"] = float(engine.last_clip_coef)
                 LOGGER.info(info)
                 sink.log(info, state["global_step"])
                 if device.type == "cuda":
