@@ -188,9 +188,13 @@ at::Tensor swiglu_bwd(const at::Tensor& dh_, const at::Tensor& gu) {
   auto dh = dh_.contiguous();
   DTG_CHECK_CUDA_BF16(gu);
   DTG_CHECK_CUDA_BF16(dh);
+  // same layout contract as swiglu_fwd: the kernel moves whole 8-element vectors, so an I that is
+  // no multiple of 8 would leave the trailing columns of both halves of dgu unwritten
+  DTG_CHECK(gu.dim() == 2 && gu.stride(1) == 1 && gu.stride(0) % 8 == 0 && gu.size(1) % 16 == 0,
+            "swiglu_bwd: gu must be [T, 2I] with I % 8 == 0");
   const int64_t T = gu.size(0);
   const int I = gu.size(1) / 2;
-  DTG_CHECK(dh.size(0) == T && dh.size(1) == I, "swiglu_bwd: shape mismatch");
+  DTG_CHECK(dh.dim() == 2 && dh.size(0) == T && dh.size(1) == I, "swiglu_bwd: shape mismatch");
   const c10::DeviceGuard g(gu.device());
   auto dgu = at::empty({T, 2 * I}, gu.options());
   const int64_t n = T * (I / 8);

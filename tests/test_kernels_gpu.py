@@ -68,9 +68,11 @@ def test_rope(cuda, D, nh):
     dops.rope_(ref, cos, sin, pos, nh, D, False)
     g = qkv.to(cuda)
     dops.rope_(g, cos.to(cuda), sin.to(cuda), pos.to(cuda), nh, D, False)
-    _close(g, ref, 2e-2, 1e-2, "rope")
+    _close(g[:, : nh * D], ref[:, : nh * D], 2e-2, 1e-2, "rope")
+    assert torch.equal(g[:, nh * D:].cpu(), qkv[:, nh * D:]), "rope touched the pass-through columns"
     dops.rope_(g, cos.to(cuda), sin.to(cuda), pos.to(cuda), nh, D, True)
-    _close(g, qkv, 3e-2, 2e-2, "rope inverse")
+    _close(g[:, : nh * D], qkv[:, : nh * D], 3e-2, 2e-2, "rope inverse")
+    assert torch.equal(g[:, nh * D:].cpu(), qkv[:, nh * D:]), "rope inverse touched the pass-through columns"
 
 
 def test_swiglu(cuda):
