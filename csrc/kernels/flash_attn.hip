@@ -27,6 +27,7 @@
 //  * Global -> register staging goes through buffer descriptors: rows past the end of a
 //    sequence read as zeros from the range check, with no per-row branches.
 #include "common.h"
+#include "flash_attn_plan.h"
 
 #include <ATen/hip/HIPGeneratorImpl.h>
 #include <ATen/hip/PhiloxUtils.cuh>
@@ -344,9 +345,6 @@ __device__ __forceinline__ void fa_stamp(long long* st, int slot, int k) {
   }
 }
 
-constexpr int kFwdBQ = 128;  // query rows per work item (4 waves x 32)
-constexpr int kFwdBK = 64;   // keys per K/V tile
-
 // WIN: sliding-window instantiation (only launched with P.window > 0); without it every window
 // term folds to a compile-time 0 and the kernel is the plain causal one.
 template <int D, bool CAUSAL, bool WIN = false, bool DROP = false>
@@ -587,11 +585,6 @@ __device__ __forceinline__ void rope_inv_rows(f32x16* acc, const float* cos_t, c
     }
   }
 }
-
-constexpr int kDqBQ = 128;  // query rows per workgroup (4 waves x 32)
-constexpr int kDqBK = 64;   // keys per K/V tile
-constexpr int kKvBK = 128;  // keys per workgroup (4 waves x 32)
-constexpr int kKvBQ = 32;   // query rows per item
 
 // dQ = scale * sum_keys dS K, query-stationary (the forward's structure).  Also writes
 // delta = rowsum(dO * O) for its rows, which bwd_dkdv_kernel (launched after it) reads.
@@ -1175,57 +1168,111 @@ __global__ __launch_bounds__(256) void bwd_kv_combine_kernel(const float* __rest
 
 }  // namespace fa
 
-// p -> keep threshold / scale (fa::DropCfg), and the Philox key / offset of this call.
-static fa::DropCfg make_drop(double p, int64_t seed, int64_t offset) {
-  DTG_CHECK(p >= 0.0 && p < 1.0, "flash_attn dropout: p must be in [0, 1)");
-  fa::DropCfg d{};
-  d.k0 = (uint32_t)((uint64_t)seed & 0xffffffffu);
-  d.k1 = (uint32_t)((uint64_t)seed >> 32) ^ (uint32_t)((uint64_t)offset >> 32);
-  d.off = (uint32_t)((uint64_t)offset & 0xffffffffu);
-  d.thr = (int)std::lround((1.0 - p) * 256.0);
-  d.thr = std::max(1, std::min(256, d.thr));
-  d.scale = 256.f / (float)d.thr;
-  return d;
-}
-
 // Launch tuning of the backward kernels, read ONCE from the environment when the extension loads
 // (DTG_FA_KV_SPLIT = N: dK/dV query-item split, 0 = auto; DTG_FA_KV_QB = 32 | 64: dK/dV query
 // rows per item; DTG_FA_OCC = 1 | 2: dQ waves per SIMD at head_dim 128; DTG_FA_KV_PF = 1 | 2:
 // dK/dV items staged ahead) -- never per launch.  Tests and A/B tools change them in-process with
-// the `flash_attn_tuning` op (dtg.ops.fa_tuning).
-struct Tuning {
-  int kv_split, kv_qb, dq_occ, kv_pf;
-};
+// the `flash_attn_tuning` op (dtg.ops.fa_tuning).  What each knob selects: flash_attn_plan.h.
 static int env_int(const char* name, int dflt) {
   const char* e = std::getenv(name);
   return (e != nullptr && e[0] != 0) ? std::atoi(e) : dflt;
 }
-static Tuning& tuning_slot() {
-  static Tuning t{std::max(0, env_int("DTG_FA_KV_SPLIT", 0)), env_int("DTG_FA_KV_QB", 64) == 32 ? 32 : 64,
-                  env_int("DTG_FA_OCC", 1) == 2 ? 2 : 1, env_int("DTG_FA_KV_PF", 1) == 2 ? 2 : 1};
+static fa::Tuning& tuning() {
+  static fa::Tuning t{std::max(0, env_int("DTG_FA_KV_SPLIT", 0)), env_int("DTG_FA_KV_QB", 64) == 32 ? 32 : 64,
+                      env_int("DTG_FA_OCC", 1) == 2 ? 2 : 1, env_int("DTG_FA_KV_PF", 1) == 2 ? 2 : 1};
   return t;
 }
-static const Tuning& tuning() { return tuning_slot(); }
-static const bool kTuningLoaded = (tuning_slot(), true);  // at library load
+[[maybe_unused]] static const bool kTuningLoaded = (tuning(), true);  // at library load
 
 // (kv_split, kv_qb) -> the previous values; a negative argument leaves that knob unchanged.
-std::vector<int64_t> flash_attn_tuning(const at::Tensor& like, int64_t kv_split, int64_t kv_qb) {
-  (void)like;
-  (void)kTuningLoaded;
-  Tuning& t = tuning_slot();
+std::vector<int64_t> flash_attn_tuning(const at::Tensor& /* like: dispatch only */, int64_t kv_split, int64_t kv_qb) {
+  fa::Tuning& t = tuning();
   std::vector<int64_t> old{t.kv_split, t.kv_qb};
   if (kv_split >= 0) t.kv_split = (int)kv_split;
-  if (kv_qb >= 0) {
-    DTG_CHECK(kv_qb == 32 || kv_qb == 64, "flash_attn_tuning: kv_qb must be 32 or 64");
-    t.kv_qb = (int)kv_qb;
-  }
+  DTG_CHECK(kv_qb < 0 || kv_qb == 32 || kv_qb == 64, "flash_attn_tuning: kv_qb must be 32 or 64");
+  if (kv_qb >= 0) t.kv_qb = (int)kv_qb;
   return old;
 }
 
-// Dynamic LDS above 64 KiB must be opted into per kernel (MI355X: 160 KiB per CU).
-static void set_lds_limit(const void* fn, size_t bytes) {
-  if (bytes > 65536) C10_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+// One launch helper per kernel family.  Each takes its dynamic-LDS size from the instantiation's own
+// template arguments and checks the plan against them; above 64 KiB it is opted into (160 KiB per CU).
+template <typename Params>
+static void launch(void (*kernel)(Params), const fa::Plan& pl, size_t lds, hipStream_t st, const Params& P) {
+  TORCH_INTERNAL_ASSERT(lds == pl.lds, "flash_attn: launch plan and instantiation disagree");
+  if (lds > 65536)
+    C10_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, dim3(pl.grid.x, pl.grid.y, pl.grid.z), dim3(256), lds, st, P);
+  DTG_LAUNCH_CHECK();
 }
+template <int D, bool C, bool WIN = false, bool DROP = false>
+static void fwd_launch(const fa::FwdPlan& pl, const fa::FwdParams& P, hipStream_t st) {
+  launch(fa::fwd_kernel<D, C, WIN, DROP>, pl, fa::fwd_lds_bytes(D), st, P);
+}
+template <int D, bool C, int OCC, bool WIN = false, bool DROP = false>
+static void dq_launch(const fa::DqPlan& pl, const fa::BwdParams& P, hipStream_t st) {
+  TORCH_INTERNAL_ASSERT(pl.occ == OCC);
+  launch(fa::bwd_dq_kernel<D, C, OCC, WIN, DROP>, pl, fa::dq_lds_bytes(D), st, P);
+}
+template <int D, bool C, int PF, bool WIN = false, int QB = fa::kKvBQ, bool DROP = false>
+static void kv_launch(const fa::KvPlan& pl, const fa::BwdParams& P, hipStream_t st) {
+  TORCH_INTERNAL_ASSERT(pl.pf == PF && pl.qb == QB);
+  launch(fa::bwd_dkdv_kernel<D, C, PF, WIN, QB, DROP>, pl, fa::kv_lds_bytes(D, QB), st, P);
+}
+
+// Plan -> instantiation, once per family, and ALL the instantiations there are: WIN is causal only, DROP
+// has no window, and the A/B forms (OCC = 2 at head_dim 128, PF = 2, QB = 32) exist for the plain kernels only.
+template <int D>
+static void launch_fwd(const fa::FwdPlan& pl, const fa::FwdParams& P, hipStream_t st) {
+  if (pl.var == fa::Variant::DROP)
+    pl.causal ? fwd_launch<D, true, false, true>(pl, P, st) : fwd_launch<D, false, false, true>(pl, P, st);
+  else if (pl.var == fa::Variant::WIN) fwd_launch<D, true, true>(pl, P, st);
+  else pl.causal ? fwd_launch<D, true>(pl, P, st) : fwd_launch<D, false>(pl, P, st);
+}
+template <int D>
+static void launch_bwd_dq(const fa::DqPlan& pl, const fa::BwdParams& P, hipStream_t st) {
+  constexpr int kOcc = D == 64 ? 2 : 1;  // head_dim 64 and the WIN / DROP forms have one occupancy each
+  if (pl.var == fa::Variant::DROP)
+    pl.causal ? dq_launch<D, true, kOcc, false, true>(pl, P, st) : dq_launch<D, false, kOcc, false, true>(pl, P, st);
+  else if (pl.var == fa::Variant::WIN) dq_launch<D, true, kOcc, true>(pl, P, st);
+  else if (pl.occ == 2) pl.causal ? dq_launch<D, true, 2>(pl, P, st) : dq_launch<D, false, 2>(pl, P, st);
+  else pl.causal ? dq_launch<D, true, kOcc>(pl, P, st) : dq_launch<D, false, kOcc>(pl, P, st);
+}
+template <int D>
+static void launch_bwd_dkdv(const fa::KvPlan& pl, fa::BwdParams P, hipStream_t st, const at::TensorOptions& opts) {
+  at::Tensor dk_part, dv_part;
+  P.nsplit = pl.nsplit;
+  if (pl.nsplit > 1) {
+    dk_part = at::empty({pl.nsplit, P.T, P.hkv, D}, opts.dtype(at::kFloat));
+    dv_part = at::empty({pl.nsplit, P.T, P.hkv, D}, opts.dtype(at::kFloat));
+    P.dk_part = dk_part.data_ptr<float>();
+    P.dv_part = dv_part.data_ptr<float>();
+  }
+  if (pl.var == fa::Variant::DROP)
+    pl.causal ? kv_launch<D, true, 1, false, 64, true>(pl, P, st) : kv_launch<D, false, 1, false, 64, true>(pl, P, st);
+  else if (pl.var == fa::Variant::WIN) kv_launch<D, true, 1, true>(pl, P, st);
+  else if (pl.pf == 2) pl.causal ? kv_launch<D, true, 2>(pl, P, st) : kv_launch<D, false, 2>(pl, P, st);
+  else if (pl.qb == 64)
+    pl.causal ? kv_launch<D, true, 1, false, 64>(pl, P, st) : kv_launch<D, false, 1, false, 64>(pl, P, st);
+  else pl.causal ? kv_launch<D, true, 1>(pl, P, st) : kv_launch<D, false, 1>(pl, P, st);
+  if (pl.nsplit > 1) {
+    const int64_t nv = P.T * P.hkv * (D / 8);
+    fa::bwd_kv_combine_kernel<D><<<(nv + 255) / 256, 256, 0, st>>>(P.dk_part, P.dv_part, pl.nsplit, P.T, P.hkv, P.scale,
+                                                                  P.dk, P.sdk, P.dv, P.sdv);
+    DTG_LAUNCH_CHECK();
+    // the split kernel's epilogue writes f32 partials: the fused RoPE backward runs on the combined dK instead
+    if (P.rope_cos != nullptr) rope_rows_launch(P.dk, P.sdk, P.hkv, D, P.rope_cos, P.rope_sin, P.rope_pos, P.T, true, st);
+  }
+}
+
+// The optional parts of an attention call; every entry point names the ones it uses ({.window = w}).
+struct AttnOpts {
+  const at::Tensor *k_start = nullptr, *k_len = nullptr;  // per-sequence key ranges, int32 [nseq]
+  int64_t max_seqlen_k = -1;                              // backward with key ranges; < 0: max_seqlen
+  int64_t window = 0;                                     // causal sliding window, 0 = none
+  const fa::DropCfg* drop = nullptr;                      // attention dropout
+  const at::Tensor *rope_cos = nullptr, *rope_sin = nullptr, *rope_pos = nullptr;  // backward: fused RoPE backward
+  at::Tensor* stamps = nullptr;                           // forward: per-workgroup timeline stamps out
+};
 
 static void check_qkv(const at::Tensor& t, const char* name, int64_t heads, int64_t d) {
   DTG_CHECK_CUDA_BF16(t);
@@ -1234,109 +1281,84 @@ static void check_qkv(const at::Tensor& t, const char* name, int64_t heads, int6
             name, " must be [T, H, D] with contiguous heads and 16-B aligned token stride");
 }
 
-// Optional per-sequence key ranges (k_start / k_len int32 [nseq]): checked, or nullptr pointers.
-static void key_range_ptrs(const at::Tensor* k_start, const at::Tensor* k_len, int nseq, const int** ks,
-                           const int** kl) {
-  *ks = *kl = nullptr;
-  if (k_start == nullptr) return;
-  for (const at::Tensor* t : {k_start, k_len})
-    DTG_CHECK(t->scalar_type() == at::kInt && t->is_cuda() && t->is_contiguous() && t->numel() == nseq,
-              "flash_attn: k_start / k_len must be int32 [nseq] on the GPU");
-  *ks = k_start->data_ptr<int>();
-  *kl = k_len->data_ptr<int>();
-}
-
-static std::tuple<at::Tensor, at::Tensor> flash_attn_fwd_impl(const at::Tensor& q, const at::Tensor& k,
-                                                              const at::Tensor& v, const at::Tensor& cu_seqlens,
-                                                              int64_t max_seqlen, double scale, bool causal,
-                                                              at::Tensor* stamps, const at::Tensor* k_start = nullptr,
-                                                              const at::Tensor* k_len = nullptr, int64_t window = 0,
-                                                              const fa::DropCfg* drop = nullptr) {
-  const int64_t T = q.size(0), hq = q.size(1), D = q.size(2), hkv = k.size(1);
-  check_qkv(q, "q", hq, D);
-  check_qkv(k, "k", hkv, D);
-  check_qkv(v, "v", hkv, D);
-  DTG_CHECK(v.size(0) == k.size(0) && (k_start != nullptr || k.size(0) == T), "flash_attn: q/k/v token counts differ");
-  DTG_CHECK(hq % hkv == 0, "flash_attn: Hq must be a multiple of Hkv");
+// The input checks the forward and the backward share: before their empty-input return ...
+static void check_inputs(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& cu_seqlens) {
+  const int64_t D = q.size(2);
+  check_qkv(q, "q", q.size(1), D);
+  check_qkv(k, "k", k.size(1), D);
+  check_qkv(v, "v", k.size(1), D);
   DTG_CHECK(D == 64 || D == 128, "flash_attn: head_dim must be 64 or 128");
   DTG_CHECK(cu_seqlens.scalar_type() == at::kInt && cu_seqlens.is_cuda() && cu_seqlens.is_contiguous(),
             "flash_attn: cu_seqlens must be int32 on the GPU");
+}
+// ... and after it: returns the call as the launch plan sees it and sets the key-range pointers, if any.
+static fa::Call checked_call(const at::Tensor& q, int64_t hkv, int nseq, int64_t max_seqlen, bool causal,
+                             const AttnOpts& op, const int** ks, const int** kl) {
+  DTG_CHECK(nseq <= 65535, "flash_attn: at most 65535 sequences per call");
+  if (op.k_start != nullptr) {
+    for (const at::Tensor* t : {op.k_start, op.k_len})
+      DTG_CHECK(t->scalar_type() == at::kInt && t->is_cuda() && t->is_contiguous() && t->numel() == nseq,
+                "flash_attn: k_start / k_len must be int32 [nseq] on the GPU");
+    *ks = op.k_start->data_ptr<int>();
+    *kl = op.k_len->data_ptr<int>();
+  }
+  DTG_CHECK(op.window >= 0 && op.window < (1ll << 30), "flash_attn: window must be >= 0 (0 = full causal)");
+  return fa::Call{(int)q.size(2), causal, op.window, op.drop != nullptr, op.k_start != nullptr, op.rope_cos != nullptr,
+                  (int)q.size(1), (int)hkv, nseq, max_seqlen, op.max_seqlen_k < 0 ? max_seqlen : op.max_seqlen_k};
+}
+
+static std::tuple<at::Tensor, at::Tensor> flash_attn_fwd_impl(
+    const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& cu_seqlens, int64_t max_seqlen,
+    double scale, bool causal, const AttnOpts& op) {
+  const int64_t T = q.size(0), hq = q.size(1), D = q.size(2), hkv = k.size(1);
+  check_inputs(q, k, v, cu_seqlens);
+  DTG_CHECK(v.size(0) == k.size(0) && (op.k_start != nullptr || k.size(0) == T), "flash_attn: q/k/v token counts differ");
+  DTG_CHECK(hq % hkv == 0, "flash_attn: Hq must be a multiple of Hkv");
   const c10::DeviceGuard g(q.device());
   auto o = at::empty({T, hq, D}, q.options());
   auto lse = at::empty({hq, T}, q.options().dtype(at::kFloat));
   const int nseq = cu_seqlens.numel() - 1;
   if (T == 0 || nseq <= 0 || max_seqlen <= 0) return {o, lse};
-  DTG_CHECK(nseq <= 65535, "flash_attn: at most 65535 sequences per call");
-  const int nqb = (int)((max_seqlen + fa::kFwdBQ - 1) / fa::kFwdBQ);
   fa::FwdParams P{bf16_ptr(q), bf16_ptr(k), bf16_ptr(v), q.stride(0), k.stride(0), v.stride(0),
                   bf16_mut(o), lse.data_ptr<float>(), cu_seqlens.data_ptr<int>(), T, (int)hq, (int)hkv,
                   (float)(scale * fa::kLog2e), nullptr, nullptr, nullptr, 0};
-  key_range_ptrs(k_start, k_len, nseq, &P.kstart, &P.klen);
-  DTG_CHECK(window >= 0 && window < (1ll << 30), "flash_attn: window must be >= 0 (0 = full causal)");
-  P.window = causal ? (int)window : 0;
-  dim3 grid(hq, nseq, nqb);
-  if (stamps != nullptr) {
-    *stamps = at::zeros({(int64_t)grid.x * grid.y * grid.z, 6}, q.options().dtype(at::kLong));
-    P.stamps = reinterpret_cast<long long*>(stamps->data_ptr<int64_t>());
+  const fa::Call c = checked_call(q, hkv, nseq, max_seqlen, causal, op, &P.kstart, &P.klen);
+  P.window = fa::window_eff(c);
+  const fa::FwdPlan pl = fa::plan_fwd(c);
+  if (op.stamps != nullptr) {
+    *op.stamps = at::zeros({(int64_t)pl.grid.x * pl.grid.y * pl.grid.z, 6}, q.options().dtype(at::kLong));
+    P.stamps = reinterpret_cast<long long*>(op.stamps->data_ptr<int64_t>());
   }
-  const size_t lds = 4 * fa::kFwdBK * D * 2;
-#define DTG_FWD(DD, C, ...)                                                               \
-  do { set_lds_limit((const void*)&fa::fwd_kernel<DD, C, ##__VA_ARGS__>, lds);               \
-       hipLaunchKernelGGL((fa::fwd_kernel<DD, C, ##__VA_ARGS__>), grid, dim3(256), lds, stream(), P); } while (0)
-  if (drop != nullptr) {  // attention dropout: the default variant's DROP instantiation
-    DTG_CHECK(P.window == 0 && P.kstart == nullptr, "flash_attn dropout: no sliding window / key ranges");
-    P.drop = *drop;
-    if (D == 128) { if (causal) DTG_FWD(128, true, false, true); else DTG_FWD(128, false, false, true); }
-    else { if (causal) DTG_FWD(64, true, false, true); else DTG_FWD(64, false, false, true); }
-  } else if (P.window > 0) {  // sliding window (causal only): the WIN instantiation
-    if (D == 128) DTG_FWD(128, true, true); else DTG_FWD(64, true, true);
-  } else if (D == 128) { if (causal) DTG_FWD(128, true); else DTG_FWD(128, false); }
-  else { if (causal) DTG_FWD(64, true); else DTG_FWD(64, false); }
-#undef DTG_FWD
-  DTG_LAUNCH_CHECK();
+  if (const char* why = fa::conflict(c)) DTG_CHECK(false, why);
+  if (op.drop != nullptr) P.drop = *op.drop;
+  D == 128 ? launch_fwd<128>(pl, P, stream()) : launch_fwd<64>(pl, P, stream());
   return {o, lse};
 }
 
-std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q, const at::Tensor& k,
-                                                  const at::Tensor& v, const at::Tensor& cu_seqlens,
-                                                  int64_t max_seqlen, double scale, bool causal, int64_t window) {
-  return flash_attn_fwd_impl(q, k, v, cu_seqlens, max_seqlen, scale, causal, nullptr, nullptr, nullptr, window);
+std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                                  const at::Tensor& cu_seqlens, int64_t max_seqlen, double scale,
+                                                  bool causal, int64_t window) {
+  return flash_attn_fwd_impl(q, k, v, cu_seqlens, max_seqlen, scale, causal, {.window = window});
 }
 
 // Diagnostic: the same launch with per-workgroup timeline stamps [start, prologue done, tile
 // loop done, stores complete, HW_ID, XCC_ID] (tools/fa_timeline.py).
-std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_fwd_stamped(const at::Tensor& q, const at::Tensor& k,
-                                                                      const at::Tensor& v,
-                                                                      const at::Tensor& cu_seqlens,
-                                                                      int64_t max_seqlen, double scale, bool causal) {
+std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_fwd_stamped(
+    const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& cu_seqlens, int64_t max_seqlen,
+    double scale, bool causal) {
   at::Tensor st;
-  auto [o, lse] = flash_attn_fwd_impl(q, k, v, cu_seqlens, max_seqlen, scale, causal, &st);
+  auto [o, lse] = flash_attn_fwd_impl(q, k, v, cu_seqlens, max_seqlen, scale, causal, {.stamps = &st});
   return {o, lse, st};
 }
 
-static void launch_bwd_dq(const fa::BwdParams& P, int64_t D, bool causal, int64_t max_seqlen, int64_t hq, int nseq,
-                          hipStream_t st, bool drop = false);
-static void launch_bwd_dkdv(fa::BwdParams P, int64_t D, bool causal, int64_t max_seqlen_k, int64_t hkv,
-                            int nseq, hipStream_t st, const at::Tensor& dk_t, const at::Tensor& dv_t, bool drop = false);
-
 // Shared backward driver: outputs are [T, H, D] views (contiguous heads, any token stride).
-struct RopeTabs {
-  const at::Tensor *cos, *sin, *pos;
-};
-
-static void flash_attn_bwd_impl(const at::Tensor& dout_, const at::Tensor& q, const at::Tensor& k,
-                                const at::Tensor& v, const at::Tensor& o, const at::Tensor& lse,
-                                const at::Tensor& cu_seqlens, int64_t max_seqlen, double scale,
-                                bool causal, const at::Tensor& dq, const at::Tensor& dk,
-                                const at::Tensor& dv, const at::Tensor* k_start = nullptr,
-                                const at::Tensor* k_len = nullptr, int64_t max_seqlen_k = -1,
-                                int64_t window = 0, const fa::DropCfg* drop = nullptr,
-                                const RopeTabs* rope = nullptr) {
+static void flash_attn_bwd_impl(const at::Tensor& dout_, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                const at::Tensor& o, const at::Tensor& lse, const at::Tensor& cu_seqlens,
+                                int64_t max_seqlen, double scale, bool causal, const at::Tensor& dq,
+                                const at::Tensor& dk, const at::Tensor& dv, const AttnOpts& op) {
   auto dout = dout_.contiguous();
   const int64_t T = q.size(0), hq = q.size(1), D = q.size(2), hkv = k.size(1);
-  check_qkv(q, "q", hq, D);
-  check_qkv(k, "k", hkv, D);
-  check_qkv(v, "v", hkv, D);
+  check_inputs(q, k, v, cu_seqlens);
   check_qkv(dq, "dq", hq, D);
   check_qkv(dk, "dk", hkv, D);
   check_qkv(dv, "dv", hkv, D);
@@ -1344,209 +1366,100 @@ static void flash_attn_bwd_impl(const at::Tensor& dout_, const at::Tensor& q, co
   DTG_CHECK(o.is_contiguous() && dout.sizes() == o.sizes() && o.size(0) == T, "flash_attn_bwd: o/dout");
   DTG_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.size(0) == hq && lse.size(1) == T,
             "flash_attn_bwd: lse must be f32 [Hq, T]");
-  DTG_CHECK(D == 64 || D == 128, "flash_attn: head_dim must be 64 or 128");
-  DTG_CHECK(cu_seqlens.scalar_type() == at::kInt && cu_seqlens.is_cuda() && cu_seqlens.is_contiguous(),
-            "flash_attn: cu_seqlens must be int32 on the GPU");
   const c10::DeviceGuard g(q.device());
-  auto opts = q.options();
   const int nseq = cu_seqlens.numel() - 1;
   // Contract: cu_seqlens covers every token (cu[-1] == T, checked by the Python wrapper), so
   // every row of dq/dk/dv is written by the kernels below -- no zero-fill pass.
   if (T == 0 || nseq <= 0 || max_seqlen <= 0) {
-    dq.zero_();
-    dk.zero_();
-    dv.zero_();
+    for (const at::Tensor& t : {dq, dk, dv}) t.zero_();
     return;
   }
-  DTG_CHECK(nseq <= 65535, "flash_attn: at most 65535 sequences per call");
-  auto delta = at::empty({hq, T}, opts.dtype(at::kFloat));
+  auto delta = at::empty({hq, T}, q.options().dtype(at::kFloat));
   fa::BwdParams P{bf16_ptr(q), bf16_ptr(k), bf16_ptr(v), bf16_ptr(dout), bf16_ptr(o), q.stride(0), k.stride(0),
                   v.stride(0), lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dq), bf16_mut(dk),
                   bf16_mut(dv), dq.stride(0), dk.stride(0), dv.stride(0), cu_seqlens.data_ptr<int>(), T, (int)hq,
                   (int)hkv, (float)scale, (float)(scale * fa::kLog2e), nullptr, nullptr, 0};
-  key_range_ptrs(k_start, k_len, nseq, &P.kstart, &P.klen);
-  DTG_CHECK(window >= 0 && window < (1ll << 30), "flash_attn: window must be >= 0 (0 = full causal)");
-  P.window = causal ? (int)window : 0;
-  if (max_seqlen_k < 0) max_seqlen_k = max_seqlen;
-  if (rope != nullptr) {
-    const at::Tensor &ct = *rope->cos, &stb = *rope->sin, &pt = *rope->pos;
+  const fa::Call c = checked_call(q, hkv, nseq, max_seqlen, causal, op, &P.kstart, &P.klen);
+  P.window = fa::window_eff(c);
+  if (op.rope_cos != nullptr) {
+    const at::Tensor &ct = *op.rope_cos, &stb = *op.rope_sin, &pt = *op.rope_pos;
     DTG_CHECK(ct.is_cuda() && ct.scalar_type() == at::kFloat && stb.scalar_type() == at::kFloat && ct.is_contiguous() &&
                   stb.is_contiguous() && ct.dim() == 2 && ct.size(1) == D / 2 && stb.sizes() == ct.sizes(),
               "flash_attn rope: tables must be contiguous f32 [max_pos, D/2] on the GPU");
     DTG_CHECK(pt.is_cuda() && pt.scalar_type() == at::kLong && pt.is_contiguous() && pt.numel() == T,
               "flash_attn rope: position ids must be int64 [T] on the GPU");
-    DTG_CHECK(P.kstart == nullptr && drop == nullptr, "flash_attn rope: self-attention without dropout only");
     P.rope_cos = ct.data_ptr<float>();
     P.rope_sin = stb.data_ptr<float>();
     P.rope_pos = pt.data_ptr<int64_t>();
   }
-  if (drop != nullptr) {
-    DTG_CHECK(P.window == 0 && P.kstart == nullptr, "flash_attn dropout: no sliding window / key ranges");
-    P.drop = *drop;
-    launch_bwd_dq(P, D, causal, max_seqlen, hq, nseq, stream(), true);
-    launch_bwd_dkdv(P, D, causal, max_seqlen_k, hkv, nseq, stream(), dk, dv, true);
-    return;
-  }
-  // (A concurrent form -- dQ on a side stream while dK/dV runs -- was slower at every shape:
-  // the pair contends for LDS bandwidth and L2, profiles/r3_s04; removed in round 6.)
-  launch_bwd_dq(P, D, causal, max_seqlen, hq, nseq, stream());
-  launch_bwd_dkdv(P, D, causal, max_seqlen_k, hkv, nseq, stream(), dk, dv);
+  if (const char* why = fa::conflict(c)) DTG_CHECK(false, why);
+  if (op.drop != nullptr) P.drop = *op.drop;
+  const fa::DqPlan dqp = fa::plan_dq(c, tuning());
+  const fa::KvPlan kvp = fa::plan_kv(c, tuning());
+  D == 128 ? launch_bwd_dq<128>(dqp, P, stream()) : launch_bwd_dq<64>(dqp, P, stream());
+  D == 128 ? launch_bwd_dkdv<128>(kvp, P, stream(), q.options()) : launch_bwd_dkdv<64>(kvp, P, stream(), q.options());
 }
 
-static void launch_bwd_dq(const fa::BwdParams& P, int64_t D, bool causal, int64_t max_seqlen, int64_t hq, int nseq,
-                          hipStream_t st, bool drop) {
-  const int occ = tuning().dq_occ;
-  {
-    dim3 grid(hq, nseq, (max_seqlen + fa::kDqBQ - 1) / fa::kDqBQ);
-    const size_t lds = 4 * fa::kDqBK * D * 2 + fa::kDqBQ * 4;  // + the per-row delta
-#define DTG_BWD_DQ(DD, C, O, ...)                                                         \
-  do { set_lds_limit((const void*)&fa::bwd_dq_kernel<DD, C, O, ##__VA_ARGS__>, lds);         \
-       hipLaunchKernelGGL((fa::bwd_dq_kernel<DD, C, O, ##__VA_ARGS__>), grid, dim3(256), lds, st, P); } while (0)
-    if (drop) {  // attention dropout (no window, delta computed here)
-      if (D == 128) { if (causal) DTG_BWD_DQ(128, true, 1, false, true); else DTG_BWD_DQ(128, false, 1, false, true); }
-      else { if (causal) DTG_BWD_DQ(64, true, 2, false, true); else DTG_BWD_DQ(64, false, 2, false, true); }
-    } else if (P.window > 0) {  // sliding window (causal only)
-      if (D == 128) DTG_BWD_DQ(128, true, 1, true); else DTG_BWD_DQ(64, true, 2, true);
-    } else if (D == 128) {
-      if (occ == 2) { if (causal) DTG_BWD_DQ(128, true, 2); else DTG_BWD_DQ(128, false, 2); }
-      else { if (causal) DTG_BWD_DQ(128, true, 1); else DTG_BWD_DQ(128, false, 1); }
-    } else { if (causal) DTG_BWD_DQ(64, true, 2); else DTG_BWD_DQ(64, false, 2); }
-#undef DTG_BWD_DQ
-    DTG_LAUNCH_CHECK();
-  }
-}
-
-static void launch_bwd_dkdv(fa::BwdParams P, int64_t D, bool causal, int64_t max_seqlen_k, int64_t hkv,
-                            int nseq, hipStream_t st, const at::Tensor& dk_t, const at::Tensor& dv_t, bool drop) {
-  // Items the dK/dV kernel stages ahead (DTG_FA_KV_PF=1|2).  Equal on MI355X once the kernel's
-  // false vmcnt waits were gone (bwd 0.767 vs 0.768 ms at the 8B shape, profiles/r1_s51_*), so
-  // the single-set form with fewer registers is the default.
-  const Tuning tn = tuning();
-  const int kv_pf = tn.kv_pf;
-  // Split the query items of each key block over several workgroups when the grid cannot fill
-  // the chip (e.g. TP = 8: one KV head per rank -> 16 x 8 workgroups for 256 CUs): aim for
-  // >= 2 workgroups per CU.  Tuning::kv_split = N forces N (1 = off).
-  const int nkb = (int)((max_seqlen_k + fa::kKvBK - 1) / fa::kKvBK);
-  const int64_t wgs = (int64_t)hkv * nseq * nkb;
-  const int kv_pf_eff = drop ? 1 : kv_pf;  // dropout: the single-set, 64-row-item instantiation
-  int nsplit = 1;
-  if (tn.kv_split > 0) nsplit = std::min(8, tn.kv_split);
-  else if (wgs > 0 && wgs < 512) nsplit = (int)std::min<int64_t>(4, (512 + wgs - 1) / wgs);
-  at::Tensor dk_part, dv_part;
-  if (nsplit > 1 && P.kstart == nullptr && P.window == 0 && kv_pf_eff == 1) {
-    dk_part = at::empty({nsplit, P.T, hkv, D}, dk_t.options().dtype(at::kFloat));
-    dv_part = at::empty({nsplit, P.T, hkv, D}, dk_t.options().dtype(at::kFloat));
-    P.dk_part = dk_part.data_ptr<float>();
-    P.dv_part = dv_part.data_ptr<float>();
-    P.nsplit = nsplit;
-  } else {
-    nsplit = 1;
-    P.nsplit = 1;
-  }
-  {
-    dim3 grid(hkv, nseq, nkb * nsplit);
-    // Tuning::kv_qb = 32 | 64: query rows per item.  64 (the two-half software pipeline) is the
-    // default: backward 2-4 % faster on every benchmarked shape, -1.9 ms per 8B step
-    // (profiles/r3_s39).  Sliding windows and the two-item prefetch keep 32.
-    const int qb = drop || (tn.kv_qb != 32 && P.window == 0 && kv_pf == 1) ? 64 : 32;
-    const size_t lds = 4 * (size_t)qb * D * 2 + 2 * 2 * qb * 4;
-#define DTG_BWD_KV(DD, C, PF, ...)                                                        \
-  do { set_lds_limit((const void*)&fa::bwd_dkdv_kernel<DD, C, PF, ##__VA_ARGS__>, lds);      \
-       hipLaunchKernelGGL((fa::bwd_dkdv_kernel<DD, C, PF, ##__VA_ARGS__>), grid, dim3(256), lds, st, P); } while (0)
-    if (drop) {
-      if (D == 128) { if (causal) DTG_BWD_KV(128, true, 1, false, 64, true); else DTG_BWD_KV(128, false, 1, false, 64, true); }
-      else { if (causal) DTG_BWD_KV(64, true, 1, false, 64, true); else DTG_BWD_KV(64, false, 1, false, 64, true); }
-    } else if (P.window > 0) {  // sliding window (causal only)
-      if (D == 128) DTG_BWD_KV(128, true, 1, true); else DTG_BWD_KV(64, true, 1, true);
-    } else if (kv_pf == 2) {
-      if (D == 128) { if (causal) DTG_BWD_KV(128, true, 2); else DTG_BWD_KV(128, false, 2); }
-      else { if (causal) DTG_BWD_KV(64, true, 2); else DTG_BWD_KV(64, false, 2); }
-    } else if (qb == 64) {
-      if (D == 128) { if (causal) DTG_BWD_KV(128, true, 1, false, 64); else DTG_BWD_KV(128, false, 1, false, 64); }
-      else { if (causal) DTG_BWD_KV(64, true, 1, false, 64); else DTG_BWD_KV(64, false, 1, false, 64); }
-    } else {
-      if (D == 128) { if (causal) DTG_BWD_KV(128, true, 1); else DTG_BWD_KV(128, false, 1); }
-      else { if (causal) DTG_BWD_KV(64, true, 1); else DTG_BWD_KV(64, false, 1); }
-    }
-#undef DTG_BWD_KV
-    DTG_LAUNCH_CHECK();
-  }
-  if (nsplit > 1) {
-    const int64_t nv = P.T * hkv * (D / 8);
-    if (D == 128)
-      fa::bwd_kv_combine_kernel<128><<<(nv + 255) / 256, 256, 0, st>>>(P.dk_part, P.dv_part, nsplit, P.T, (int)hkv,
-                                                                      P.scale, P.dk, P.sdk, P.dv, P.sdv);
-    else
-      fa::bwd_kv_combine_kernel<64><<<(nv + 255) / 256, 256, 0, st>>>(P.dk_part, P.dv_part, nsplit, P.T, (int)hkv,
-                                                                     P.scale, P.dk, P.sdk, P.dv, P.sdv);
-    DTG_LAUNCH_CHECK();
-    // the split kernel's epilogue writes f32 partials: the fused RoPE backward runs on the
-    // combined dK instead
-    if (P.rope_cos != nullptr) rope_rows_launch(P.dk, P.sdk, (int)hkv, (int)D, P.rope_cos, P.rope_sin, P.rope_pos, P.T, true, st);
-  }
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_bwd(
-    const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-    const at::Tensor& o, const at::Tensor& lse, const at::Tensor& cu_seqlens, int64_t max_seqlen,
-    double scale, bool causal, int64_t window) {
+// Fresh dq, dk, dv for [T, H, D] inputs; with key ranges, keys outside every range keep zero dK / dV.
+static std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_bwd_alloc(
+    const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
+    const at::Tensor& lse, const at::Tensor& cu_seqlens, int64_t max_seqlen, double scale, bool causal,
+    const AttnOpts& op) {
   auto dq = at::empty(q.sizes(), q.options());
-  auto dk = at::empty(k.sizes(), k.options());
-  auto dv = at::empty(v.sizes(), v.options());
-  flash_attn_bwd_impl(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, causal, dq, dk, dv, nullptr, nullptr, -1,
-                      window);
+  auto dk = op.k_start != nullptr ? at::zeros(k.sizes(), k.options()) : at::empty(k.sizes(), k.options());
+  auto dv = op.k_start != nullptr ? at::zeros(v.sizes(), v.options()) : at::empty(v.sizes(), v.options());
+  flash_attn_bwd_impl(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, causal, dq, dk, dv, op);
   return {dq, dk, dv};
 }
 
 // q, k, v are head slices of one fused [T, (nq + 2 nkv) * D] projection output; the gradient
 // comes back in the same fused layout so the QKV GEMM backward consumes it directly.
-at::Tensor flash_attn_bwd_qkv(const at::Tensor& dout, const at::Tensor& qkv, int64_t nq, int64_t nkv,
-                              int64_t head_dim, const at::Tensor& o, const at::Tensor& lse,
-                              const at::Tensor& cu_seqlens, int64_t max_seqlen, double scale, bool causal,
-                              int64_t window) {
+static at::Tensor flash_attn_bwd_fused(const char* name, const at::Tensor& dout, const at::Tensor& qkv, int64_t nq,
+                                       int64_t nkv, int64_t D, const at::Tensor& o, const at::Tensor& lse,
+                                       const at::Tensor& cu_seqlens, int64_t max_seqlen, double scale, bool causal,
+                                       const AttnOpts& op) {
   DTG_CHECK_CUDA_BF16(qkv);
-  const int64_t T = qkv.size(0), D = head_dim;
-  DTG_CHECK(qkv.dim() == 2 && qkv.size(1) == (nq + 2 * nkv) * D && qkv.stride(1) == 1,
-            "flash_attn_bwd_qkv: qkv must be [T, (nq + 2 nkv) * D]");
+  const int64_t T = qkv.size(0);
+  DTG_CHECK(qkv.dim() == 2 && qkv.size(1) == (nq + 2 * nkv) * D && qkv.stride(1) == 1, name,
+            ": qkv must be [T, (nq + 2 nkv) * D]");
   auto dqkv = at::empty({T, (nq + 2 * nkv) * D}, qkv.options());
   auto view3 = [&](const at::Tensor& t, int64_t h0, int64_t nh) {
     return t.as_strided({T, nh, D}, {t.stride(0), D, 1}, t.storage_offset() + h0 * D);
   };
-  flash_attn_bwd_impl(dout, view3(qkv, 0, nq), view3(qkv, nq, nkv), view3(qkv, nq + nkv, nkv), o, lse,
-                      cu_seqlens, max_seqlen, scale, causal, view3(dqkv, 0, nq), view3(dqkv, nq, nkv),
-                      view3(dqkv, nq + nkv, nkv), nullptr, nullptr, -1, window);
+  flash_attn_bwd_impl(dout, view3(qkv, 0, nq), view3(qkv, nq, nkv), view3(qkv, nq + nkv, nkv), o, lse, cu_seqlens,
+                      max_seqlen, scale, causal, view3(dqkv, 0, nq), view3(dqkv, nq, nkv), view3(dqkv, nq + nkv, nkv), op);
   return dqkv;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_bwd(
+    const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
+    const at::Tensor& lse, const at::Tensor& cu_seqlens, int64_t max_seqlen, double scale, bool causal, int64_t window) {
+  return flash_attn_bwd_alloc(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, causal, {.window = window});
+}
+
+at::Tensor flash_attn_bwd_qkv(const at::Tensor& dout, const at::Tensor& qkv, int64_t nq, int64_t nkv, int64_t head_dim,
+                              const at::Tensor& o, const at::Tensor& lse, const at::Tensor& cu_seqlens,
+                              int64_t max_seqlen, double scale, bool causal, int64_t window) {
+  return flash_attn_bwd_fused("flash_attn_bwd_qkv", dout, qkv, nq, nkv, head_dim, o, lse, cu_seqlens, max_seqlen, scale,
+                              causal, {.window = window});
 }
 
 // flash_attn_bwd_qkv with the RoPE backward of the q and k heads fused into the dQ / dK
 // epilogues (replaces rope_(dqkv, cos, sin, pos, nq + nkv, D, inverse = true) after it).
-at::Tensor flash_attn_bwd_qkv_rope(const at::Tensor& dout, const at::Tensor& qkv, int64_t nq, int64_t nkv,
-                                   int64_t head_dim, const at::Tensor& o, const at::Tensor& lse,
-                                   const at::Tensor& cu_seqlens, int64_t max_seqlen, double scale, bool causal,
-                                   const at::Tensor& cos_t, const at::Tensor& sin_t, const at::Tensor& pos,
-                                   int64_t window) {
-  DTG_CHECK_CUDA_BF16(qkv);
-  const int64_t T = qkv.size(0), D = head_dim;
-  DTG_CHECK(qkv.dim() == 2 && qkv.size(1) == (nq + 2 * nkv) * D && qkv.stride(1) == 1,
-            "flash_attn_bwd_qkv_rope: qkv must be [T, (nq + 2 nkv) * D]");
-  auto dqkv = at::empty({T, (nq + 2 * nkv) * D}, qkv.options());
-  auto view3 = [&](const at::Tensor& t, int64_t h0, int64_t nh) {
-    return t.as_strided({T, nh, D}, {t.stride(0), D, 1}, t.storage_offset() + h0 * D);
-  };
-  const RopeTabs rt{&cos_t, &sin_t, &pos};
-  flash_attn_bwd_impl(dout, view3(qkv, 0, nq), view3(qkv, nq, nkv), view3(qkv, nq + nkv, nkv), o, lse,
-                      cu_seqlens, max_seqlen, scale, causal, view3(dqkv, 0, nq), view3(dqkv, nq, nkv),
-                      view3(dqkv, nq + nkv, nkv), nullptr, nullptr, -1, window, nullptr, &rt);
-  return dqkv;
+at::Tensor flash_attn_bwd_qkv_rope(const at::Tensor& dout, const at::Tensor& qkv, int64_t nq, int64_t nkv, int64_t head_dim,
+                                   const at::Tensor& o, const at::Tensor& lse, const at::Tensor& cu_seqlens,
+                                   int64_t max_seqlen, double scale, bool causal, const at::Tensor& cos_t,
+                                   const at::Tensor& sin_t, const at::Tensor& pos, int64_t window) {
+  return flash_attn_bwd_fused("flash_attn_bwd_qkv_rope", dout, qkv, nq, nkv, head_dim, o, lse, cu_seqlens, max_seqlen,
+                              scale, causal, {.window = window, .rope_cos = &cos_t, .rope_sin = &sin_t, .rope_pos = &pos});
 }
 
 // FlashAttention-2-style varlen over explicit per-sequence key ranges (context parallelism).
-std::tuple<at::Tensor, at::Tensor> flash_attn_varlen_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                                                         const at::Tensor& cu_seqlens_q, const at::Tensor& k_start,
-                                                         const at::Tensor& k_len, int64_t max_seqlen_q,
-                                                         int64_t max_seqlen_k, double scale, bool causal) {
-  (void)max_seqlen_k;  // the forward grid spans query blocks only
-  return flash_attn_fwd_impl(q, k, v, cu_seqlens_q, max_seqlen_q, scale, causal, nullptr, &k_start, &k_len);
+std::tuple<at::Tensor, at::Tensor> flash_attn_varlen_fwd(
+    const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& cu_seqlens_q,
+    const at::Tensor& k_start, const at::Tensor& k_len, int64_t max_seqlen_q,
+    int64_t /* max_seqlen_k: the forward grid spans query blocks only */, double scale, bool causal) {
+  return flash_attn_fwd_impl(q, k, v, cu_seqlens_q, max_seqlen_q, scale, causal, {.k_start = &k_start, .k_len = &k_len});
 }
 
 // Key ranges must be disjoint; keys outside every range get zero dK / dV.
@@ -1554,22 +1467,21 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_varlen_bwd(
     const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
     const at::Tensor& lse, const at::Tensor& cu_seqlens_q, const at::Tensor& k_start, const at::Tensor& k_len,
     int64_t max_seqlen_q, int64_t max_seqlen_k, double scale, bool causal) {
-  auto dq = at::empty(q.sizes(), q.options());
-  auto dk = at::zeros(k.sizes(), k.options());
-  auto dv = at::zeros(v.sizes(), v.options());
-  flash_attn_bwd_impl(dout, q, k, v, o, lse, cu_seqlens_q, max_seqlen_q, scale, causal, dq, dk, dv, &k_start, &k_len,
-                      max_seqlen_k);
-  return {dq, dk, dv};
+  return flash_attn_bwd_alloc(dout, q, k, v, o, lse, cu_seqlens_q, max_seqlen_q, scale, causal,
+                              {.k_start = &k_start, .k_len = &k_len, .max_seqlen_k = max_seqlen_k});
 }
 
 // Attention-probability dropout (GPT-2 attn_pdrop): p and the Philox key / offset of this call as
 // an int64 [2] device tensor {seed, offset} (dtg::philox_rng draws it from torch's CUDA generator,
 // graph-safe); the backward regenerates the same keep mask from the same tensor (see fa::DropCfg).
 static fa::DropCfg make_drop_dev(double p, const at::Tensor& rng, const at::Tensor& like) {
+  DTG_CHECK(p >= 0.0 && p < 1.0, "flash_attn dropout: p must be in [0, 1)");
   DTG_CHECK(rng.is_cuda() && rng.scalar_type() == at::kLong && rng.numel() == 2 && rng.is_contiguous() &&
                 rng.device() == like.device(),
             "flash_attn dropout: rng must be a contiguous int64 [2] tensor {seed, offset} on the inputs' device");
-  fa::DropCfg d = make_drop(p, 0, 0);
+  fa::DropCfg d{};
+  d.thr = std::max(1, std::min(256, (int)std::lround((1.0 - p) * 256.0)));
+  d.scale = 256.f / (float)d.thr;
   d.rng = reinterpret_cast<const uint32_t*>(rng.data_ptr<int64_t>());
   return d;
 }
@@ -1578,7 +1490,7 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd_drop(const at::Tensor& q, cons
                                                        const at::Tensor& cu_seqlens, int64_t max_seqlen, double scale,
                                                        bool causal, double p, const at::Tensor& rng) {
   const fa::DropCfg d = make_drop_dev(p, rng, q);
-  return flash_attn_fwd_impl(q, k, v, cu_seqlens, max_seqlen, scale, causal, nullptr, nullptr, nullptr, 0, &d);
+  return flash_attn_fwd_impl(q, k, v, cu_seqlens, max_seqlen, scale, causal, {.drop = &d});
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_bwd_drop(
@@ -1586,31 +1498,15 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_bwd_drop(
     const at::Tensor& lse, const at::Tensor& cu_seqlens, int64_t max_seqlen, double scale, bool causal, double p,
     const at::Tensor& rng) {
   const fa::DropCfg d = make_drop_dev(p, rng, q);
-  auto dq = at::empty(q.sizes(), q.options());
-  auto dk = at::empty(k.sizes(), k.options());
-  auto dv = at::empty(v.sizes(), v.options());
-  flash_attn_bwd_impl(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, causal, dq, dk, dv, nullptr, nullptr, -1, 0,
-                      &d);
-  return {dq, dk, dv};
+  return flash_attn_bwd_alloc(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, causal, {.drop = &d});
 }
 
-at::Tensor flash_attn_bwd_qkv_drop(const at::Tensor& dout, const at::Tensor& qkv, int64_t nq, int64_t nkv,
-                                   int64_t head_dim, const at::Tensor& o, const at::Tensor& lse,
-                                   const at::Tensor& cu_seqlens, int64_t max_seqlen, double scale, bool causal,
-                                   double p, const at::Tensor& rng) {
-  DTG_CHECK_CUDA_BF16(qkv);
+at::Tensor flash_attn_bwd_qkv_drop(const at::Tensor& dout, const at::Tensor& qkv, int64_t nq, int64_t nkv, int64_t head_dim,
+                                   const at::Tensor& o, const at::Tensor& lse, const at::Tensor& cu_seqlens,
+                                   int64_t max_seqlen, double scale, bool causal, double p, const at::Tensor& rng) {
   const fa::DropCfg d = make_drop_dev(p, rng, qkv);
-  const int64_t T = qkv.size(0), D = head_dim;
-  DTG_CHECK(qkv.dim() == 2 && qkv.size(1) == (nq + 2 * nkv) * D && qkv.stride(1) == 1,
-            "flash_attn_bwd_qkv_drop: qkv must be [T, (nq + 2 nkv) * D]");
-  auto dqkv = at::empty({T, (nq + 2 * nkv) * D}, qkv.options());
-  auto view3 = [&](const at::Tensor& t, int64_t h0, int64_t nh) {
-    return t.as_strided({T, nh, D}, {t.stride(0), D, 1}, t.storage_offset() + h0 * D);
-  };
-  flash_attn_bwd_impl(dout, view3(qkv, 0, nq), view3(qkv, nq, nkv), view3(qkv, nq + nkv, nkv), o, lse, cu_seqlens,
-                      max_seqlen, scale, causal, view3(dqkv, 0, nq), view3(dqkv, nq, nkv), view3(dqkv, nq + nkv, nkv),
-                      nullptr, nullptr, -1, 0, &d);
-  return dqkv;
+  return flash_attn_bwd_fused("flash_attn_bwd_qkv_drop", dout, qkv, nq, nkv, head_dim, o, lse, cu_seqlens, max_seqlen,
+                              scale, causal, {.drop = &d});
 }
 
 // {seed, offset} of one dropout call from torch's CUDA generator for `like`'s device, written into

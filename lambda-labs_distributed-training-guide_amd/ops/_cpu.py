@@ -346,12 +346,18 @@ def flash_attn_bwd_drop(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, ca
     return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
 
 
-def flash_attn_bwd_qkv_drop(dout, qkv, nq, nkv, head_dim, o, lse, cu_seqlens, max_seqlen, scale, causal, p, rng):
+def _qkv_heads(qkv, nq, nkv, d):
+    """q [T, nq, d], k and v [T, nkv, d] of a fused [T, (nq + 2 nkv) * d] activation."""
     T = qkv.shape[0]
-    d = head_dim
     q = qkv[:, : nq * d].reshape(T, nq, d)
     k = qkv[:, nq * d : (nq + nkv) * d].reshape(T, nkv, d)
     v = qkv[:, (nq + nkv) * d :].reshape(T, nkv, d)
+    return q, k, v
+
+
+def flash_attn_bwd_qkv_drop(dout, qkv, nq, nkv, head_dim, o, lse, cu_seqlens, max_seqlen, scale, causal, p, rng):
+    T = qkv.shape[0]
+    q, k, v = _qkv_heads(qkv, nq, nkv, head_dim)
     dq, dk, dv = flash_attn_bwd_drop(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, causal, p, rng)
     return torch.cat([dq.reshape(T, -1), dk.reshape(T, -1), dv.reshape(T, -1)], dim=1)
 
@@ -411,10 +417,7 @@ def flash_attn_varlen_bwd(dout, q, k, v, o, lse, cu_seqlens_q, k_start, k_len, m
 
 def flash_attn_bwd_qkv(dout, qkv, nq, nkv, head_dim, o, lse, cu_seqlens, max_seqlen, scale, causal, window=0):
     T = qkv.shape[0]
-    d = head_dim
-    q = qkv[:, : nq * d].reshape(T, nq, d)
-    k = qkv[:, nq * d : (nq + nkv) * d].reshape(T, nkv, d)
-    v = qkv[:, (nq + nkv) * d :].reshape(T, nkv, d)
+    q, k, v = _qkv_heads(qkv, nq, nkv, head_dim)
     dq, dk, dv = flash_attn_bwd(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, causal, window)
     return torch.cat([dq.reshape(T, -1), dk.reshape(T, -1), dv.reshape(T, -1)], dim=1)
 

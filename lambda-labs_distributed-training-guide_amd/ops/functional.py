@@ -205,6 +205,16 @@ def rope_tables(head_dim, theta, max_pos, scaling=None, device=None):
 _FA_ROPE_FUSED = os.environ.get("DTG_FA_ROPE_FUSED", "1") == "1"
 
 
+def _qkv_head_views(qkv, nq, nkv, d):
+    """q [T, nq, d], k and v [T, nkv, d]: strided head views of a fused [T, (nq + 2 nkv) * d]."""
+    T = qkv.shape[0]
+
+    def view(h0, nh):
+        return qkv.as_strided((T, nh, d), (qkv.stride(0), d, 1), qkv.storage_offset() + h0 * d)
+
+    return view(0, nq), view(nq, nkv), view(nq + nkv, nkv)
+
+
 class _AttentionQKV(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, cos, sin, pos, cu_seqlens, max_seqlen, nq, nkv, head_dim, scale, causal, rope, window):
@@ -212,9 +222,7 @@ class _AttentionQKV(torch.autograd.Function):
         d = head_dim
         if rope:
             ops.rope_(qkv, cos, sin, pos, nq + nkv, d, False)
-        q = qkv.as_strided((T, nq, d), (qkv.stride(0), d, 1), qkv.storage_offset())
-        k = qkv.as_strided((T, nkv, d), (qkv.stride(0), d, 1), qkv.storage_offset() + nq * d)
-        v = qkv.as_strided((T, nkv, d), (qkv.stride(0), d, 1), qkv.storage_offset() + (nq + nkv) * d)
+        q, k, v = _qkv_head_views(qkv, nq, nkv, d)
         o, lse = ops.flash_attn_fwd(q, k, v, cu_seqlens, max_seqlen, scale, causal, window)
         ctx.save_for_backward(qkv, o, lse, cu_seqlens, cos, sin, pos)
         ctx.meta = (max_seqlen, nq, nkv, d, scale, causal, rope, window)
@@ -247,9 +255,7 @@ class _AttentionQKVDrop(torch.autograd.Function):
     def forward(ctx, qkv, cu_seqlens, max_seqlen, nq, nkv, head_dim, scale, causal, p, rng):
         T = qkv.shape[0]
         d = head_dim
-        q = qkv.as_strided((T, nq, d), (qkv.stride(0), d, 1), qkv.storage_offset())
-        k = qkv.as_strided((T, nkv, d), (qkv.stride(0), d, 1), qkv.storage_offset() + nq * d)
-        v = qkv.as_strided((T, nkv, d), (qkv.stride(0), d, 1), qkv.storage_offset() + (nq + nkv) * d)
+        q, k, v = _qkv_head_views(qkv, nq, nkv, d)
         o, lse = ops.flash_attn_fwd_drop(q, k, v, cu_seqlens, max_seqlen, scale, causal, p, rng)
         ctx.save_for_backward(qkv, o, lse, cu_seqlens, rng)
         ctx.meta = (max_seqlen, nq, nkv, d, scale, causal, p)
