@@ -2,13 +2,22 @@
 
 Semantics match HF GPT2LMHeadModel: learned positions, pre-LayerNorm blocks,
 fused QKV projection with bias, GELU-tanh MLP, dropout 0.1, tied lm_head.  Attention uses
-the same varlen flash kernel as Llama (head_dim 64); LayerNorm/GELU/dropout are ATen ops
-(GPT-2 is the plumbing model, the hot-path kernels target the Llama family).  Linear weights
-are stored [out, in] (HF's Conv1D stores [in, out]; `hf_compat` transposes).
+the same varlen flash kernel as Llama (head_dim 64).  Linear weights are stored [out, in]
+(HF's Conv1D stores [in, out]; `hf_compat` transposes).
+
+On bf16 GPU activations with n_embd % 8 == 0 the block's streaming passes run the gfx950
+kernels of csrc/kernels/layernorm.hip and gelu.hip (`FUSED`, DTG_GPT2_FUSED=0 turns it off):
+ln_1 / ln_f are `ops.layer_norm`; the attention branch's residual dropout, the residual add and
+ln_2 are one `ops.dropout_add_layer_norm` (Philox keep mask regenerated in the backward, no mask
+stored); the MLP is one `ops.gelu_mlp` node whose backward writes the transposed operands of
+both weight-gradient GEMMs.  The MLP branch's dropout + add and the embedding dropout stay ATen.
+Everywhere else (CPU, other dtypes, FUSED off) the ATen ops run: F.layer_norm, F.gelu,
+F.dropout in the order below.
 """
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -17,6 +26,12 @@ import torch.nn.functional as F
 from .. import ops
 from .config import GPT2Config
 from .llama import CausalLMOutput, Weight
+
+FUSED = os.environ.get("DTG_GPT2_FUSED", "1") == "1"
+
+
+def _fused(x):
+    return FUSED and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.shape[-1] % 8 == 0
 
 
 class _LN(nn.Module):
@@ -27,6 +42,8 @@ class _LN(nn.Module):
         self.bias = nn.Parameter(torch.empty(n, device=device, dtype=dtype))
 
     def forward(self, x):
+        if _fused(x):
+            return ops.layer_norm(x, self.weight, self.bias, self.eps)
         return F.layer_norm(x, (x.shape[-1],), self.weight, self.bias, self.eps)
 
 
@@ -62,6 +79,10 @@ class GPT2Block(nn.Module):
         # attention-probability dropout (attn_pdrop, 0.1 in training) runs inside the flash
         # kernels: Philox keep mask drawn in the forward, regenerated in the backward
         a = ops.attention(qkv, self.nh, self.nh, self.d, cu, max_seqlen, dropout_p=p_attn)
+        if _fused(x):
+            y, x = ops.dropout_add_layer_norm(self.c_proj(a), x, self.ln_2.weight, self.ln_2.bias, self.ln_2.eps, p_res)
+            m = ops.gelu_mlp(y, self.c_fc.weight, self.c_fc.bias, self.mlp_proj.weight, self.mlp_proj.bias)
+            return x + F.dropout(m, p_res, self.training)
         x = x + F.dropout(self.c_proj(a), p_res, self.training)
         m = self.mlp_proj(F.gelu(self.c_fc(self.ln_2(x)), approximate="tanh"))
         return x + F.dropout(m, p_res, self.training)

@@ -346,6 +346,125 @@ def flash_attn_bwd_drop(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, ca
     return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
 
 
+# ---- LayerNorm with fused dropout + residual add, GELU-tanh (csrc/kernels/layernorm.hip, gelu.hip)
+_LN_STREAM_TAG = 0x4C4E4452
+
+
+def ln_dropout_keep(seed, offset, T, H, p):
+    """bool [T, H]: the keep decision of element (row, col) -- byte (col & 3) of word
+    ((col >> 2) & 1) of Philox4x32-10({col >> 3, row, offset lo, "LNDR"}, key = {seed lo,
+    seed hi ^ offset hi}) < thr.  The counter layout of layernorm.hip, bit for bit."""
+    import numpy as np
+
+    thr, _ = dropout_threshold(p)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    offset = int(offset) & 0xFFFFFFFFFFFFFFFF
+    rows = np.arange(T, dtype=np.uint64)[:, None]
+    chunks = np.arange(H // 8, dtype=np.uint64)[None, :]
+    shape = (T, H // 8)
+    w = philox4x32_10(np.broadcast_to(chunks, shape), np.broadcast_to(rows, shape),
+                      np.full(shape, offset & 0xFFFFFFFF, dtype=np.uint64),
+                      np.full(shape, _LN_STREAM_TAG, dtype=np.uint64), seed & 0xFFFFFFFF, (seed >> 32) ^ (offset >> 32))
+    byte = np.stack([(w[j >> 2] >> np.uint64(8 * (j & 3))) & np.uint64(255) for j in range(8)], axis=-1)
+    return torch.from_numpy((byte.astype(np.int64) < thr).reshape(T, H))
+
+
+def _ln_check_rows(t, name):
+    """check_rows of layernorm.hip: 2-D, unit inner stride, 16-B aligned rows, H % 8 == 0."""
+    if not (t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0):
+        raise RuntimeError(f"dtg: {name} must be 2-D with unit inner stride and 16-byte aligned rows")
+    if t.shape[1] % 8:
+        raise RuntimeError("dtg: layernorm: bad weight/hidden")
+    if t.shape[1] > 16384:
+        raise RuntimeError("dtg: layernorm: unsupported hidden size")
+
+
+def _ln_drop(p, rng):
+    if not 0.0 <= p < 1.0:
+        raise RuntimeError("dtg: layernorm dropout: p must be in [0, 1)")
+    if p == 0.0:
+        if rng is not None:
+            raise RuntimeError("dtg: layernorm dropout: rng given with p == 0")
+        return None
+    if rng is None:
+        raise RuntimeError("dtg: layernorm dropout: rng must be a contiguous int64 [2] tensor {seed, offset}")
+    return _rng_pair(rng)
+
+
+def _ln_stats(h, eps):
+    """Two-pass f32 mean and rstd of the rows (the kernel's order: mean, then the centred squares)."""
+    hf = h.float()
+    mean = hf.mean(-1)
+    d = hf - mean[:, None]
+    return mean, torch.rsqrt((d * d).mean(-1) + eps)
+
+
+def layernorm_fwd(x, w, b, eps):
+    _ln_check_rows(x, "x")
+    mean, rstd = _ln_stats(x, eps)
+    return F.layer_norm(x, (x.shape[1],), w, b, eps), mean, rstd
+
+
+def dropout_add_layernorm_fwd(x, res, w, b, eps, p, rng):
+    _ln_check_rows(x, "x")
+    _ln_check_rows(res, "residual")
+    so = _ln_drop(p, rng)
+    xf = x.float()
+    if so is not None:
+        keep = ln_dropout_keep(so[0], so[1], x.shape[0], x.shape[1], p)
+        xf = torch.where(keep, xf * dropout_threshold(p)[1], torch.zeros_like(xf))
+    h = (res.float() + xf).to(x.dtype)
+    y, mean, rstd = layernorm_fwd(h, w, b, eps)
+    return y, h, mean, rstd
+
+
+def layernorm_bwd(dy, h, w, mean, rstd, dres, p, rng):
+    _ln_check_rows(h, "h")
+    so = _ln_drop(p, rng)
+    dyf, wf, r = dy.float(), w.float(), rstd[:, None]
+    n = (h.float() - mean[:, None]) * r
+    g = dyf * wf
+    dhf = r * (g - g.mean(-1, keepdim=True) - n * (g * n).mean(-1, keepdim=True))
+    if dres is not None:
+        dhf = dhf + dres.float()
+    dh = dhf.to(h.dtype)
+    dx = dh
+    if so is not None:
+        keep = ln_dropout_keep(so[0], so[1], h.shape[0], h.shape[1], p)
+        dx = torch.where(keep, dhf * dropout_threshold(p)[1], torch.zeros_like(dhf)).to(h.dtype)
+    return dh, dx, (dyf * n).sum(0).to(w.dtype), dyf.sum(0).to(w.dtype)
+
+
+_GELU_C = math.sqrt(2.0 / math.pi)
+_GELU_A = 0.044715
+
+
+def _gelu_check(x, name):
+    if not (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.shape[1] % 8 == 0):
+        raise RuntimeError(f"dtg: {name}: x must be [T, I] with unit inner stride, 16-byte aligned rows and I % 8 == 0")
+
+
+def gelu_fwd(x):
+    _gelu_check(x, "gelu_fwd")
+    return F.gelu(x, approximate="tanh").contiguous()
+
+
+def gelu_bwd(dh, x):
+    """dh * (sigma + x sigma (1 - sigma) 2u'), sigma = sigmoid(2u): the kernel's closed form."""
+    _gelu_check(x, "gelu_bwd")
+    xf = x.float()
+    s = torch.sigmoid(2 * _GELU_C * (xf + _GELU_A * xf * xf * xf))
+    du2 = 2 * _GELU_C * (1 + 3 * _GELU_A * xf * xf)
+    return (dh.float() * (s + xf * s * (1 - s) * du2)).to(x.dtype)
+
+
+def gelu_bwd_t(dh, x):
+    if x.shape[0] % 8:
+        raise RuntimeError("dtg: gelu_bwd_t: T must be a multiple of 8")
+    dx = gelu_bwd(dh, x)
+    return dx, dx.t().contiguous(), gelu_fwd(x).t().contiguous()
+
+
 def _qkv_heads(qkv, nq, nkv, d):
     """q [T, nq, d], k and v [T, nkv, d] of a fused [T, (nq + 2 nkv) * d] activation."""
     T = qkv.shape[0]
@@ -471,6 +590,7 @@ for _name, _fn in list(globals().items()):
         "ce_fwd_bwd_", "ce_stats", "ce_grad_", "adamw_", "adamw_t_", "grad_sumsq_", "flash_attn_fwd", "flash_attn_bwd",
         "flash_attn_bwd_qkv", "transpose2d", "transpose_mats_", "swiglu_bwd_t", "embedding_bwd_", "flash_attn_varlen_fwd",
         "flash_attn_varlen_bwd", "flash_attn_fwd_drop", "flash_attn_bwd_drop", "flash_attn_bwd_qkv_drop", "philox_rng",
-        "flash_attn_bwd_qkv_rope", "flash_attn_tuning",
+        "flash_attn_bwd_qkv_rope", "flash_attn_tuning", "layernorm_fwd", "dropout_add_layernorm_fwd", "layernorm_bwd",
+        "gelu_fwd", "gelu_bwd", "gelu_bwd_t",
     ):
         LIB.impl(_name, _fn, "CPU")

@@ -13,6 +13,18 @@ _DEFS = [
     "rmsnorm_fwd(Tensor x, Tensor w, float eps) -> (Tensor, Tensor)",
     "add_rmsnorm_fwd(Tensor x, Tensor residual, Tensor w, float eps) -> (Tensor, Tensor, Tensor)",
     "rmsnorm_bwd(Tensor dy, Tensor x, Tensor w, Tensor rstd, Tensor? dres) -> (Tensor, Tensor)",
+    # LayerNorm (GPT-2): y, mean, rstd; the fused form first makes h = residual + dropout(x) (keep mask
+    # from Philox(rng), nothing stored; rng = None iff p == 0) and returns y, h, mean, rstd.  The
+    # backward returns dh, dx (the dropped branch's gradient; dh itself when p == 0), dw, db.
+    "layernorm_fwd(Tensor x, Tensor w, Tensor b, float eps) -> (Tensor, Tensor, Tensor)",
+    "dropout_add_layernorm_fwd(Tensor x, Tensor residual, Tensor w, Tensor b, float eps, float p, Tensor? rng) "
+    "-> (Tensor, Tensor, Tensor, Tensor)",
+    "layernorm_bwd(Tensor dy, Tensor h, Tensor w, Tensor mean, Tensor rstd, Tensor? dres, float p, Tensor? rng) "
+    "-> (Tensor, Tensor, Tensor, Tensor)",
+    # GELU-tanh; gelu_bwd_t also returns dx^T and gelu(x)^T (the TN operands of the MLP's dW GEMMs)
+    "gelu_fwd(Tensor x) -> Tensor",
+    "gelu_bwd(Tensor dh, Tensor x) -> Tensor",
+    "gelu_bwd_t(Tensor dh, Tensor x) -> (Tensor, Tensor, Tensor)",
     "rope_(Tensor(a!) qkv, Tensor cos, Tensor sin, Tensor pos, int nheads, int head_dim, bool inverse) -> ()",
     "swiglu_fwd(Tensor gu) -> Tensor",
     "swiglu_bwd(Tensor dh, Tensor gu) -> Tensor",

@@ -157,6 +157,55 @@ def add_rms_norm(x, res, w, eps):
 
 
 # --------------------------------------------------------------------------------------------
+# LayerNorm and fused dropout + residual-add + LayerNorm (GPT-2)
+# --------------------------------------------------------------------------------------------
+class _LayerNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, eps):
+        y, mean, rstd = ops.layernorm_fwd(x, w, b, eps)
+        ctx.save_for_backward(x, w, b, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, b, mean, rstd = ctx.saved_tensors
+        dx, _, dw, db = ops.layernorm_bwd(dy, x, w, mean, rstd, None, 0.0, None)
+        return dx, route_param_grad(w, dw), route_param_grad(b, db), None
+
+
+class _DropoutAddLayerNorm(torch.autograd.Function):
+    """y = layernorm(h), h = res + dropout(x, p), one pass each way.  The keep mask is a Philox
+    function of (rng, row, column), regenerated in the backward (no mask stored); `rng` is the
+    device tensor of `dropout_rng`, so a captured HIP graph draws a new mask every replay."""
+
+    @staticmethod
+    def forward(ctx, x, res, w, b, eps, p, rng):
+        y, h, mean, rstd = ops.dropout_add_layernorm_fwd(x, res, w, b, eps, p, rng)
+        saved = (h, w, b, mean, rstd) if rng is None else (h, w, b, mean, rstd, rng)
+        ctx.save_for_backward(*saved)
+        ctx.p = p
+        return y, h
+
+    @staticmethod
+    def backward(ctx, dy, dh_in):
+        h, w, b, mean, rstd, *rng = ctx.saved_tensors
+        if dy is None:
+            dy = torch.zeros_like(h)
+        dh, dx, dw, db = ops.layernorm_bwd(dy, h, w, mean, rstd, dh_in, ctx.p, rng[0] if rng else None)
+        return dx, dh, route_param_grad(w, dw), route_param_grad(b, db), None, None, None
+
+
+def layer_norm(x, w, b, eps):
+    return _LayerNorm.apply(x, w, b, eps)
+
+
+def dropout_add_layer_norm(x, res, w, b, eps, p=0.0):
+    """Returns (layernorm(h), h) with h = res + dropout(x, p); draws its own rng when p > 0."""
+    p = float(p)
+    return _DropoutAddLayerNorm.apply(x, res, w, b, eps, p, dropout_rng(x) if p > 0.0 else None)
+
+
+# --------------------------------------------------------------------------------------------
 # Rotary tables
 # --------------------------------------------------------------------------------------------
 def _llama3_inv_freq(inv_freq, scaling):
@@ -419,6 +468,57 @@ def swiglu_mlp(x, w_gu, w_down, out=None):
     """Llama MLP: down_proj(silu(gate(x)) * up(x)) with the fused [gate; up] weight.  `out`: see
     `linear`."""
     return _SwiGLUMLP.apply(x, w_gu, w_down, None if out is None else (out,))
+
+
+# --------------------------------------------------------------------------------------------
+# GELU MLP (GPT-2)
+# --------------------------------------------------------------------------------------------
+class _GeluMLP(torch.autograd.Function):
+    """proj(gelu_tanh(x @ W_fc^T + b_fc)) + b_proj as one autograd node, shaped like _SwiGLUMLP.
+
+    Saves x and the pre-activation a (h = gelu(a) is recomputed in backward).  On the TN path the
+    backward's GELU kernel writes da together with da^T and h^T, the token-contiguous operands
+    of the two weight-gradient GEMMs, so the transposes _LinearBias would spend around the GELU
+    never run.  The bias gradients are f32 column sums as in _LinearBias."""
+
+    @staticmethod
+    def forward(ctx, x, w_fc, b_fc, w_proj, b_proj):
+        a = torch.addmm(b_fc, x, w_fc.t())
+        h = ops.gelu_fwd(a)
+        ctx.save_for_backward(x, w_fc, b_fc, w_proj, b_proj, a)
+        return torch.addmm(b_proj, h, w_proj.t())
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w_fc, b_fc, w_proj, b_proj, a = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx_tn, dw_tn = _bwd_layout(x, w_fc)
+        fused = dw_tn and _tn_ok(dy, a) and a.stride(0) == a.shape[1]
+        db_proj = route_param_grad(b_proj, dy.sum(0, dtype=torch.float32).to(dy.dtype))
+        dh = torch.mm(dy, _wt(w_proj).t()) if dx_tn else torch.mm(dy, w_proj)
+        if fused:
+            da, da_t, h_t = ops.gelu_bwd_t(dh, a)
+            del dh
+            dw_proj = route_weight_grad_mm(w_proj, dy, None, a_t=ops.transpose2d(dy), b_t=h_t)
+            del h_t
+        else:
+            h = ops.gelu_fwd(a)
+            da = ops.gelu_bwd(dh, a)
+            del dh
+            dw_proj = route_weight_grad_mm(w_proj, dy, h)
+            del h
+        db_fc = route_param_grad(b_fc, da.sum(0, dtype=torch.float32).to(da.dtype))
+        dx = torch.mm(da, _wt(w_fc).t()) if dx_tn else torch.mm(da, w_fc)
+        if fused:
+            dw_fc = route_weight_grad_mm(w_fc, da, x, a_t=da_t, b_t=ops.transpose2d(x))
+        else:
+            dw_fc = route_weight_grad_mm(w_fc, da, x)
+        return dx, dw_fc, db_fc, dw_proj, db_proj
+
+
+def gelu_mlp(x, w_fc, b_fc, w_proj, b_proj):
+    """GPT-2 MLP: c_proj(gelu_tanh(c_fc(x))), both projections with bias."""
+    return _GeluMLP.apply(x, w_fc, b_fc, w_proj, b_proj)
 
 
 # --------------------------------------------------------------------------------------------
