@@ -31,6 +31,8 @@ ALIASES = {
     "qwen/qwen2.5-0.5b": "qwen2.5-0.5b",
     "qwen/qwen2.5-7b": "qwen2.5-7b",
     "mistralai/mistral-7b-v0.3": "mistral-7b-v0.3",
+    "qwen/qwen3-0.6b": "qwen3-0.6b",
+    "qwen/qwen3-8b": "qwen3-8b",
 }
 
 
@@ -51,10 +53,12 @@ class LlamaConfig:
     initializer_range: float = 0.02
     eos_token_id: Optional[int] = None
     hf_name: str = ""
-    # llama (Llama-2/3/3.1/3.2), mistral (Llama layout + sliding-window attention), qwen2 (+ q/k/v bias)
+    # llama (Llama-2/3/3.1/3.2), mistral (Llama layout + sliding-window attention), qwen2 (+ q/k/v bias),
+    # qwen3 (+ per-head q/k RMSNorm, explicit head_dim, no bias)
     model_type: str = "llama"
     attention_bias: bool = False  # q/k/v projection bias (Qwen2); o_proj never has one here
     sliding_window: Optional[int] = None  # Mistral: keys within this distance (None = full causal)
+    qk_norm: bool = False  # Qwen3: RMSNorm over head_dim on every q and k head, before RoPE
 
     def __post_init__(self):
         if self.head_dim is None:
@@ -66,6 +70,8 @@ class LlamaConfig:
         attn = h * (self.num_attention_heads + 2 * self.num_key_value_heads) * d + self.num_attention_heads * d * h
         if self.attention_bias:
             attn += (self.num_attention_heads + 2 * self.num_key_value_heads) * d
+        if self.qk_norm:
+            attn += 2 * d
         layer = attn + 3 * h * i + 2 * h
         return v * h * (1 if self.tie_word_embeddings else 2) + L * layer + h
 
@@ -116,11 +122,11 @@ class GPT2Config:
         return 6 * (self.num_params() - self.n_positions * self.n_embd) + 6 * self.n_layer * self.n_embd * seq_len
 
 
-LLAMA_FAMILY = ("llama", "mistral", "qwen2")
+LLAMA_FAMILY = ("llama", "mistral", "qwen2", "qwen3")
 
 
 def _from_dict(d: dict):
-    """HF config dict -> our config.  The Llama layout covers llama, mistral and qwen2
+    """HF config dict -> our config.  The Llama layout covers llama, mistral, qwen2 and qwen3
     (RMSNorm, RoPE, GQA, SwiGLU); anything else is refused instead of silently mis-built."""
     d = dict(d)
     mt = d.get("model_type", "llama")
@@ -130,6 +136,10 @@ def _from_dict(d: dict):
         cls = LlamaConfig
         if mt == "qwen2":
             d.setdefault("attention_bias", True)  # Qwen2 always has q/k/v biases
+            if not d.get("use_sliding_window", False):
+                d["sliding_window"] = None
+        if mt == "qwen3":
+            d.setdefault("qk_norm", True)  # Qwen3 always norms its q and k heads; no q/k/v bias by default
             if not d.get("use_sliding_window", False):
                 d["sliding_window"] = None
         if mt == "llama":

@@ -52,6 +52,9 @@ def llama_from_hf(hf_sd: dict, cfg: LlamaConfig) -> dict:
             out[f"layers.{i}.self_attn.qkv_proj.bias"] = torch.cat(
                 [hf_sd[p + "self_attn.q_proj.bias"], hf_sd[p + "self_attn.k_proj.bias"],
                  hf_sd[p + "self_attn.v_proj.bias"]], 0)[:, None]
+        for nm in ("q_norm", "k_norm"):  # Qwen3
+            if p + f"self_attn.{nm}.weight" in hf_sd:
+                out[f"layers.{i}.self_attn.{nm}.weight"] = hf_sd[p + f"self_attn.{nm}.weight"]
         out[f"layers.{i}.self_attn.o_proj.weight"] = hf_sd[p + "self_attn.o_proj.weight"]
         out[f"layers.{i}.mlp.gate_up_proj.weight"] = torch.cat([hf_sd[p + "mlp.gate_proj.weight"], hf_sd[p + "mlp.up_proj.weight"]], 0)
         out[f"layers.{i}.mlp.down_proj.weight"] = hf_sd[p + "mlp.down_proj.weight"]
@@ -83,7 +86,7 @@ def gpt2_to_hf(sd: dict, cfg: GPT2Config) -> dict:
 
 
 def hf_llama_config(cfg: LlamaConfig):
-    """The transformers config of the same architecture (LlamaConfig / MistralConfig / Qwen2Config)."""
+    """The transformers config of the same architecture (LlamaConfig / MistralConfig / Qwen2Config / Qwen3Config)."""
     common = dict(
         vocab_size=cfg.vocab_size, hidden_size=cfg.hidden_size, intermediate_size=cfg.intermediate_size,
         num_hidden_layers=cfg.num_hidden_layers, num_attention_heads=cfg.num_attention_heads,
@@ -94,6 +97,11 @@ def hf_llama_config(cfg: LlamaConfig):
         from transformers import Qwen2Config
 
         return Qwen2Config(use_sliding_window=cfg.sliding_window is not None, sliding_window=cfg.sliding_window, **common)
+    if cfg.model_type == "qwen3":
+        from transformers import Qwen3Config
+
+        return Qwen3Config(head_dim=cfg.head_dim, attention_bias=cfg.attention_bias,
+                           use_sliding_window=cfg.sliding_window is not None, sliding_window=cfg.sliding_window, **common)
     if cfg.model_type == "mistral":
         from transformers import MistralConfig
 
@@ -106,6 +114,8 @@ def hf_llama_config(cfg: LlamaConfig):
 def hf_causal_lm_class(cfg: LlamaConfig):
     import transformers
 
+    if cfg.model_type == "qwen3":
+        return transformers.Qwen3ForCausalLM
     return {"qwen2": transformers.Qwen2ForCausalLM, "mistral": transformers.MistralForCausalLM}.get(
         cfg.model_type, transformers.LlamaForCausalLM)
 

@@ -89,10 +89,43 @@ class LlamaAttention(nn.Module):
                                                           dtype=dtype))
         self.o_proj = Weight(h, self.nq * self.d, device=device, dtype=dtype)
         self.window = int(cfg.sliding_window or 0)
+        self.qk_norm = bool(cfg.qk_norm)
+        if self.qk_norm:  # Qwen3: RMSNorm over head_dim on every q / k head before RoPE, one weight each
+            self.eps = cfg.rms_norm_eps
+            self.q_norm = Weight(self.d, device=device, dtype=dtype)
+            self.k_norm = Weight(self.d, device=device, dtype=dtype)
+            for p in (self.q_norm.weight, self.k_norm.weight):
+                # replicated over TP while each rank sums over its local heads: grads need the TP all-reduce
+                p._dtg_sequence_parallel = tp.enabled
+
+    def _forward_qk_norm(self, qkv, rc: RunCtx):
+        """The three attention paths with the fused per-head norm (+ RoPE) ahead of the attention."""
+        wq, wk, d = self.q_norm.weight, self.k_norm.weight, self.d
+        if rc.cp_group is not None:  # the fused pass replaces ops.rope
+            from ..parallel.context_parallel import cp_attention
+
+            T = qkv.shape[0]
+            qkv = ops.qk_norm_rope(qkv, wq, wk, self.eps, self.nq, self.nkv, d, rc.cos, rc.sin, rc.pos)
+            q = qkv[:, :self.nq * d].reshape(T, self.nq, d)
+            k = qkv[:, self.nq * d:(self.nq + self.nkv) * d].reshape(T, self.nkv, d)
+            v = qkv[:, (self.nq + self.nkv) * d:].reshape(T, self.nkv, d)
+            return cp_attention(q, k, v, rc.cp_group, rc.rows, ranges=rc.cp_ranges).reshape(T, self.nq * d)
+        if rc.sp_group is not None:  # Ulysses: norm only on the local slice (per token and head, so it
+            # commutes with the exchange); the attention after the all-to-all keeps roping
+            from ..parallel.ulysses import ulysses_attention
+
+            qkv = ops.qk_norm_rope(qkv, wq, wk, self.eps, self.nq, self.nkv, d)
+            return ulysses_attention(qkv, self.nq, self.nkv, d, rc.sp_group, rc.rows, rc.cu_seqlens,
+                                     rc.max_seqlen, rc.cos, rc.sin, rc.pos)
+        qkv = ops.qk_norm_rope(qkv, wq, wk, self.eps, self.nq, self.nkv, d, rc.cos, rc.sin, rc.pos,
+                               grad_inplace=True)  # the attention backward's dQKV is this node's alone
+        return ops.attention(qkv, self.nq, self.nkv, d, rc.cu_seqlens, rc.max_seqlen, window=self.window)
 
     def forward(self, x, rc: RunCtx, out=None):
         b = getattr(self.qkv_proj, "bias", None)
         qkv = ops.linear(x, self.qkv_proj.weight, None if b is None else b.view(-1))
+        if self.qk_norm:
+            return ops.linear(self._forward_qk_norm(qkv, rc), self.o_proj.weight, out=out)
         if rc.cp_group is not None:  # context parallel: zig-zag sequence shards
             from ..parallel.context_parallel import cp_attention
 
@@ -271,7 +304,7 @@ class LlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def init_param(self, name: str, t: torch.Tensor):
         """HF Llama init: normal(0, initializer_range) for matrices/embeddings, ones for norms."""
-        if name.endswith("layernorm.weight") or name == "norm.weight":
+        if name.endswith("layernorm.weight") or name == "norm.weight" or name.endswith(("q_norm.weight", "k_norm.weight")):
             t.fill_(1.0)
         elif name.endswith(".bias"):
             t.zero_()

@@ -144,6 +144,8 @@ def _row_width(name: str, cfg, tp_size: int):
     """Columns of our TP-local parameter (None for 1-D)."""
     if name.endswith("layernorm.weight") or name == "norm.weight":
         return None
+    if name.endswith("self_attn.q_norm.weight") or name.endswith("self_attn.k_norm.weight"):
+        return None  # Qwen3 per-head norms: [head_dim], replicated over TP
     if name.endswith("qkv_proj.bias"):
         return 1  # stored as a [rows, 1] column
     if name.endswith("self_attn.o_proj.weight"):

@@ -24,6 +24,7 @@ from .functional import (  # noqa: E402
     gelu_mlp,
     layer_norm,
     linear,
+    qk_norm_rope,
     rms_norm,
     rope,
     rope_tables,
@@ -54,5 +55,5 @@ def fa_tuning(device="cuda", kv_split: int = -1, kv_qb: int = -1):
 __all__ = [
     "add_rms_norm", "attention", "rope", "embedding", "fused_linear_cross_entropy", "linear", "rms_norm",
     "rope_tables", "swiglu", "swiglu_mlp", "vocab_parallel_fused_linear_cross_entropy", "route_param_grad", "adamw_step",
-    "fa_tuning", "layer_norm", "dropout_add_layer_norm", "gelu_mlp",
+    "fa_tuning", "layer_norm", "dropout_add_layer_norm", "gelu_mlp", "qk_norm_rope",
 ]

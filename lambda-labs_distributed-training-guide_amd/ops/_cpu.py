@@ -55,6 +55,47 @@ def rope_(qkv, cos, sin, pos, nheads, head_dim, inverse):
     qkv[:, : nheads * head_dim] = torch.cat([o1, o2], dim=-1).to(qkv.dtype).reshape(T, nheads * head_dim)
 
 
+def _qk_weights(wq, wk, nq, nkv):
+    """[nq + nkv, D] f32: the q weight for the q heads, the k weight for the k heads."""
+    return torch.cat([wq.float()[None].expand(nq, -1), wk.float()[None].expand(nkv, -1)], 0)
+
+
+def _qk_rotate(y, cos, sin, pos, inverse):
+    """rope_'s rotation of [T, heads, D] f32 values (pairs (i, i + D/2)); empty tables: identity."""
+    if cos.numel() == 0:
+        return y
+    half = y.shape[-1] // 2
+    c = cos[pos][:, None, :]
+    s = sin[pos][:, None, :]
+    if inverse:
+        s = -s
+    y1, y2 = y[..., :half], y[..., half:]
+    return torch.cat([y1 * c - y2 * s, y2 * c + y1 * s], -1)
+
+
+def qk_norm_rope_fwd_(qkv, wq, wk, cos, sin, pos, nq, nkv, head_dim, eps):
+    """y = w * x * rsqrt(mean(x^2) + eps) per (token, head), then rope_'s rotation, all in f32 with one
+    rounding on the in-place store; returns the pre-norm q|k and rstd (csrc/kernels/qk_norm.hip)."""
+    T, nh, d = qkv.shape[0], nq + nkv, head_dim
+    xqk = qkv[:, : nh * d].clone()
+    x = xqk.float().reshape(T, nh, d)
+    rstd = torch.rsqrt(x.pow(2).mean(-1) + eps)
+    y = _qk_weights(wq, wk, nq, nkv) * (x * rstd[..., None])
+    qkv[:, : nh * d] = _qk_rotate(y, cos, sin, pos, False).reshape(T, nh * d).to(qkv.dtype)
+    return xqk, rstd
+
+
+def qk_norm_rope_bwd_(dqkv, xqk, rstd, wq, wk, cos, sin, pos, nq, nkv, head_dim):
+    T, nh, d = dqkv.shape[0], nq + nkv, head_dim
+    dy = _qk_rotate(dqkv[:, : nh * d].float().reshape(T, nh, d), cos, sin, pos, True)
+    xh = xqk.float().reshape(T, nh, d) * rstd.reshape(T, nh, 1)
+    g = _qk_weights(wq, wk, nq, nkv) * dy
+    dx = rstd.reshape(T, nh, 1) * (g - xh * (g * xh).mean(-1, keepdim=True))
+    dw = dy * xh  # before the in-place store: for f32 inputs without rotation dy is a view of dqkv
+    dqkv[:, : nh * d] = dx.reshape(T, nh * d).to(dqkv.dtype)
+    return dw[:, :nq].sum((0, 1)).to(wq.dtype), dw[:, nq:].sum((0, 1)).to(wk.dtype)
+
+
 def swiglu_fwd(gu):
     inter = gu.shape[1] // 2
     g, u = gu[:, :inter].float(), gu[:, inter:].float()
@@ -591,6 +632,6 @@ for _name, _fn in list(globals().items()):
         "flash_attn_bwd_qkv", "transpose2d", "transpose_mats_", "swiglu_bwd_t", "embedding_bwd_", "flash_attn_varlen_fwd",
         "flash_attn_varlen_bwd", "flash_attn_fwd_drop", "flash_attn_bwd_drop", "flash_attn_bwd_qkv_drop", "philox_rng",
         "flash_attn_bwd_qkv_rope", "flash_attn_tuning", "layernorm_fwd", "dropout_add_layernorm_fwd", "layernorm_bwd",
-        "gelu_fwd", "gelu_bwd", "gelu_bwd_t",
+        "gelu_fwd", "gelu_bwd", "gelu_bwd_t", "qk_norm_rope_fwd_", "qk_norm_rope_bwd_",
     ):
         LIB.impl(_name, _fn, "CPU")

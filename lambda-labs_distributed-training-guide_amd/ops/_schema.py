@@ -26,6 +26,13 @@ _DEFS = [
     "gelu_bwd(Tensor dh, Tensor x) -> Tensor",
     "gelu_bwd_t(Tensor dh, Tensor x) -> (Tensor, Tensor, Tensor)",
     "rope_(Tensor(a!) qkv, Tensor cos, Tensor sin, Tensor pos, int nheads, int head_dim, bool inverse) -> ()",
+    # per-head RMSNorm of the q and k heads of a fused QKV activation + RoPE, in place (Qwen3); empty
+    # cos / sin = norm only.  fwd returns (xqk: the pre-norm q|k [T, (nq + nkv) * D], rstd f32 [T, nq + nkv]);
+    # bwd turns the gradient w.r.t. the rotated q / k into dx in place and returns (dwq, dwk)
+    "qk_norm_rope_fwd_(Tensor(a!) qkv, Tensor wq, Tensor wk, Tensor cos, Tensor sin, Tensor pos, int nq, int nkv, "
+    "int head_dim, float eps) -> (Tensor, Tensor)",
+    "qk_norm_rope_bwd_(Tensor(a!) dqkv, Tensor xqk, Tensor rstd, Tensor wq, Tensor wk, Tensor cos, Tensor sin, "
+    "Tensor pos, int nq, int nkv, int head_dim) -> (Tensor, Tensor)",
     "swiglu_fwd(Tensor gu) -> Tensor",
     "swiglu_bwd(Tensor dh, Tensor gu) -> Tensor",
     "swiglu_bwd_t(Tensor dh, Tensor gu) -> (Tensor, Tensor, Tensor)",

@@ -352,6 +352,88 @@ def rope(qkv, cos, sin, pos, nheads, head_dim):
 FA_HEAD_DIMS = (64, 128)  # head dims the flash-attention kernels are instantiated for
 
 
+# --------------------------------------------------------------------------------------------
+# Per-head QK RMSNorm + RoPE (Qwen3), one pass each way (csrc/kernels/qk_norm.hip)
+# --------------------------------------------------------------------------------------------
+# DTG_QKNORM_FUSED=0 takes the composed path below instead (a copy, the norms in torch, the
+# separate RoPE pass): the fused kernel's A/B partner and the yardstick of its accuracy tests.
+_QKNORM_FUSED = os.environ.get("DTG_QKNORM_FUSED", "1") == "1"
+
+
+class _QKNormRope(torch.autograd.Function):
+    """y = rope(w * x * rstd) on the q and k heads of a fused QKV activation, in place (v untouched).
+    Saves the pre-norm q|k copy the kernel writes and rstd; the backward turns the gradient w.r.t.
+    the rotated q / k (what the attention backward without RoPE returns) into dx, in place when
+    `grad_inplace` says the incoming gradient belongs to this node alone, else on a copy."""
+
+    @staticmethod
+    def forward(ctx, qkv, wq, wk, cos, sin, pos, nq, nkv, head_dim, eps, grad_inplace):
+        xqk, rstd = ops.qk_norm_rope_fwd_(qkv, wq, wk, cos, sin, pos, nq, nkv, head_dim, eps)
+        ctx.mark_dirty(qkv)
+        ctx.save_for_backward(xqk, rstd, wq, wk, cos, sin, pos)
+        ctx.meta = (nq, nkv, head_dim, grad_inplace)
+        return qkv
+
+    @staticmethod
+    def backward(ctx, dqkv):
+        xqk, rstd, wq, wk, cos, sin, pos = ctx.saved_tensors
+        nq, nkv, d, grad_inplace = ctx.meta
+        dense = dqkv.dim() == 2 and dqkv.stride(1) == 1 and dqkv.stride(0) >= dqkv.shape[1] and dqkv.stride(0) % 8 == 0
+        if not (grad_inplace and dense):
+            dqkv = dqkv.contiguous().clone() if dense else dqkv.contiguous()
+        dwq, dwk = ops.qk_norm_rope_bwd_(dqkv, xqk, rstd, wq, wk, cos, sin, pos, nq, nkv, d)
+        return (dqkv, route_param_grad(wq, dwq), route_param_grad(wk, dwk), None, None, None, None, None, None, None,
+                None)
+
+
+class _RoutedParam(torch.autograd.Function):
+    """Identity on a parameter whose gradient goes through route_param_grad (for torch-composed paths)."""
+
+    @staticmethod
+    def forward(ctx, w):
+        ctx.w = w
+        return w.view_as(w)
+
+    @staticmethod
+    def backward(ctx, g):
+        return route_param_grad(ctx.w, g.to(ctx.w.dtype))
+
+
+def _qk_norm_rope_composed(qkv, wq, wk, eps, nq, nkv, d, cos, sin, pos):
+    """The same function from torch ops, out of place: the q|k heads copied out and widened, RMSNorm
+    over head_dim and rope_'s rotation in f32, one rounding back to the activation dtype (the fused
+    kernel's numerics, so the two agree to the rounding of one store); autograd differentiates it."""
+    T, nh = qkv.shape[0], nq + nkv
+    xf = qkv[:, : nh * d].reshape(T, nh, d).float()
+    n = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
+    wq, wk = _RoutedParam.apply(wq).float(), _RoutedParam.apply(wk).float()
+    y = torch.cat([wq * n[:, :nq], wk * n[:, nq:]], 1)
+    if cos is not None:
+        h = d // 2
+        c, s = cos[pos][:, None, :], sin[pos][:, None, :]
+        y1, y2 = y[..., :h], y[..., h:]
+        y = torch.cat([y1 * c - y2 * s, y2 * c + y1 * s], -1)
+    return torch.cat([y.reshape(T, nh * d).to(qkv.dtype), qkv[:, nh * d:]], 1)
+
+
+def qk_norm_rope(qkv, wq, wk, eps, nq, nkv, head_dim, cos=None, sin=None, pos=None, grad_inplace=False):
+    """Qwen3's per-head RMSNorm of the q and k heads of a fused [T, (nq + 2 nkv) * d] activation
+    (weights wq / wk [d], shared by all heads), followed by RoPE when cos / sin / pos are given
+    (norm only otherwise).  One fused pass, in place on `qkv`; follow it with `attention(...)`
+    WITHOUT cos / sin / pos.  `grad_inplace`: the backward may overwrite the incoming gradient
+    (true when the only consumer is `attention`, whose backward returns a fresh fused dQKV).
+    GPU head dims without a kernel instantiation, and DTG_QKNORM_FUSED=0, take the composed path."""
+    nq, nkv, d = int(nq), int(nkv), int(head_dim)
+    if not _QKNORM_FUSED or (qkv.is_cuda and d not in FA_HEAD_DIMS):
+        return _qk_norm_rope_composed(qkv, wq, wk, float(eps), nq, nkv, d, cos, sin, pos)
+    if cos is None:
+        cos = sin = torch.empty(0, device=qkv.device)
+        pos = torch.empty(0, dtype=torch.long, device=qkv.device)
+    if qkv.is_leaf and qkv.requires_grad:  # a leaf cannot be written in place
+        qkv = qkv.clone()
+    return _QKNormRope.apply(qkv, wq, wk, cos, sin, pos, nq, nkv, d, float(eps), bool(grad_inplace))
+
+
 def _attention_padded(qkv, nq, nkv, d, cu_seqlens, max_seqlen, cos, sin, pos, causal, scale, window):
     """Head dims without a kernel instantiation (e.g. 80, 96, 48): zero-pad every head to the next
     instantiated width.  Zero columns add nothing to q.k (the scale keeps 1/sqrt(d) of the true
