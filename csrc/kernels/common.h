@@ -77,6 +77,24 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
   return r;
 }
 
+// Sums of two values over the workgroup; `scratch` holds 2 * blockDim.x / 64 floats.
+__device__ __forceinline__ void block_sum2(float& a, float& b, float* scratch) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  a = wave_sum(a);
+  b = wave_sum(b);
+  __syncthreads();
+  if (lane == 0) {
+    scratch[2 * wid] = a;
+    scratch[2 * wid + 1] = b;
+  }
+  __syncthreads();
+  a = b = 0.f;
+  for (int i = 0; i < nw; ++i) {
+    a += scratch[2 * i];
+    b += scratch[2 * i + 1];
+  }
+}
+
 __device__ __forceinline__ float block_max(float v, float* scratch) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
   v = wave_max(v);

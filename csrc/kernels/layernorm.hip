@@ -24,13 +24,13 @@
 // backward walks rows_per_block rows per workgroup, software-pipelined, and writes f32 partials
 // of dw and db that a second kernel column-reduces in a fixed order (no atomics, bitwise
 // reproducible).
-#include "common.h"
+#include "norm_common.h"
 #include "philox.h"
 
 namespace dtg {
 namespace ln {
 
-constexpr int kThreads = 256;
+using norm::kThreads;
 constexpr uint32_t kStreamTag = 0x4C4E4452u;  // "LNDR": keeps this stream apart from the attention mask's
 
 // The 8 keep decisions of chunk `chunk` of row `row`: bit j = column 8 * chunk + j is kept.
@@ -41,24 +41,6 @@ __device__ __forceinline__ uint32_t keep_bits(const philox::Key& k, int row, int
 #pragma unroll
   for (int j = 0; j < 8; ++j) bits |= ((int)((c[j >> 2] >> (8 * (j & 3))) & 255u) < thr ? 1u : 0u) << j;
   return bits;
-}
-
-// Sums of two values over the workgroup; `scratch` holds 2 * blockDim.x / 64 floats.
-__device__ __forceinline__ void block_sum2(float& a, float& b, float* scratch) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  a = wave_sum(a);
-  b = wave_sum(b);
-  __syncthreads();
-  if (lane == 0) {
-    scratch[2 * wid] = a;
-    scratch[2 * wid + 1] = b;
-  }
-  __syncthreads();
-  a = b = 0.f;
-  for (int i = 0; i < nw; ++i) {
-    a += scratch[2 * i];
-    b += scratch[2 * i + 1];
-  }
 }
 
 // MODE 0: h = x.  MODE 1: h = bf16(x + residual).  MODE 2: h = bf16(residual + keep * x * scale).
@@ -225,63 +207,10 @@ __global__ __launch_bounds__(kThreads) void layernorm_bwd_kernel(
   for (int i = 0; i < PER; ++i) {
     const int c = threadIdx.x + i * kThreads;
     if (c < nch) {
-      float4* dst = reinterpret_cast<float4*>(dw_part + (int64_t)blockIdx.x * H + c * 8);
-      dst[0] = make_float4(dwacc[i][0], dwacc[i][1], dwacc[i][2], dwacc[i][3]);
-      dst[1] = make_float4(dwacc[i][4], dwacc[i][5], dwacc[i][6], dwacc[i][7]);
-      dst = reinterpret_cast<float4*>(db_part + (int64_t)blockIdx.x * H + c * 8);
-      dst[0] = make_float4(dbacc[i][0], dbacc[i][1], dbacc[i][2], dbacc[i][3]);
-      dst[1] = make_float4(dbacc[i][4], dbacc[i][5], dbacc[i][6], dbacc[i][7]);
+      norm::store8f(dw_part + (int64_t)blockIdx.x * H + c * 8, dwacc[i]);
+      norm::store8f(db_part + (int64_t)blockIdx.x * H + c * 8, dbacc[i]);
     }
   }
-}
-
-// Column sums of the two [nrows, H] f32 partial matrices (blockIdx.y: 0 = dw, 1 = db) -> bf16
-// [2, H], fixed summation order.  The reduction of rmsnorm.hip: 16 columns x 16 row groups per
-// workgroup, combined through LDS.
-constexpr int kColsumCols = 16;
-__global__ __launch_bounds__(256) void colsum2_to_bf16_kernel(const float* __restrict__ part, int nrows, int H,
-                                                              uint16_t* __restrict__ out) {
-  constexpr int G = 256 / kColsumCols;
-  __shared__ float red[G][kColsumCols + 1];
-  const int lane = threadIdx.x % kColsumCols, grp = threadIdx.x / kColsumCols;
-  const int c = blockIdx.x * kColsumCols + lane;
-  part += (int64_t)blockIdx.y * nrows * H;
-  float s = 0.f;
-  if (c < H)
-    for (int r = grp; r < nrows; r += G) s += part[(int64_t)r * H + c];
-  red[grp][lane] = s;
-  __syncthreads();
-  if (grp == 0 && c < H) {
-    float t = 0.f;
-#pragma unroll
-    for (int g = 0; g < G; ++g) t += red[g][lane];
-    out[(int64_t)blockIdx.y * H + c] = f2bf(t);
-  }
-}
-
-static int pick_per(int H) {
-  const int nch = H / 8;
-  const int per = (nch + kThreads - 1) / kThreads;
-  if (per <= 1) return 1;
-  if (per <= 2) return 2;
-  if (per <= 4) return 4;
-  if (per <= 8) return 8;
-  return -1;
-}
-
-#define DTG_LN_PER_DISPATCH(per, ...)                    \
-  switch (per) {                                         \
-    case 1: { constexpr int P = 1; __VA_ARGS__; break; } \
-    case 2: { constexpr int P = 2; __VA_ARGS__; break; } \
-    case 4: { constexpr int P = 4; __VA_ARGS__; break; } \
-    case 8: { constexpr int P = 8; __VA_ARGS__; break; } \
-    default: DTG_CHECK(false, "layernorm: unsupported hidden size"); \
-  }
-
-static void check_rows(const at::Tensor& t, const char* name) {
-  DTG_CHECK_CUDA_BF16(t);
-  DTG_CHECK(t.dim() == 2 && t.stride(1) == 1 && t.stride(0) % 8 == 0, name,
-            " must be 2-D with unit inner stride and 16-byte aligned rows");
 }
 
 static void check_affine(const at::Tensor& w, const at::Tensor* b, int H) {
@@ -319,81 +248,80 @@ static Drop make_drop(double p, const c10::optional<at::Tensor>& rng, const at::
 
 }  // namespace ln
 
-std::tuple<at::Tensor, at::Tensor, at::Tensor> layernorm_fwd(const at::Tensor& x, const at::Tensor& w,
-                                                             const at::Tensor& b, double eps) {
-  ln::check_rows(x, "x");
+template <int MODE>
+static void launch_layernorm_fwd(int per, const at::Tensor& x, const at::Tensor& res, const at::Tensor& w,
+                                 const at::Tensor& b, at::Tensor& y, at::Tensor& h, at::Tensor& mean, at::Tensor& rstd,
+                                 int T, int H, double eps, const ln::Drop& d) {
+  DTG_PER_DISPATCH("layernorm", per,
+                   ln::layernorm_fwd_kernel<P, MODE><<<T, ln::kThreads, 0, stream()>>>(
+                       bf16_ptr(x), x.stride(0), MODE ? bf16_ptr(res) : nullptr, MODE ? res.stride(0) : 0, bf16_ptr(w),
+                       bf16_ptr(b), bf16_mut(y), MODE ? bf16_mut(h) : nullptr, mean.data_ptr<float>(),
+                       rstd.data_ptr<float>(), H, (float)eps, d.thr, d.scale, d.rng));
+}
+
+// layernorm_fwd (ADD = false: `res` is not read, h stays undefined, no dropout) and
+// dropout_add_layernorm_fwd: y, h, mean, rstd.
+template <bool ADD>
+static std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> layernorm_fwd_impl(
+    const at::Tensor& x, const at::Tensor& res, const at::Tensor& w, const at::Tensor& b, double eps, double p,
+    const c10::optional<at::Tensor>& rng) {
+  norm::check_rows(x, "x");
+  if (ADD) norm::check_rows(res, "residual");
   const int T = x.size(0), H = x.size(1);
+  if (ADD) DTG_CHECK(res.size(0) == T && res.size(1) == H, "dropout_add_layernorm: shape mismatch");
   ln::check_affine(w, &b, H);
+  const ln::Drop d = ln::make_drop(p, rng, x);
   const c10::DeviceGuard g(x.device());
   auto y = at::empty({T, H}, x.options());
+  auto h = ADD ? at::empty({T, H}, x.options()) : at::Tensor();
   auto mean = at::empty({T}, x.options().dtype(at::kFloat));
   auto rstd = at::empty({T}, x.options().dtype(at::kFloat));
-  if (T == 0) return {y, mean, rstd};
-  const int per = ln::pick_per(H);
-  DTG_LN_PER_DISPATCH(per, ln::layernorm_fwd_kernel<P, 0><<<T, ln::kThreads, 0, stream()>>>(
-                               bf16_ptr(x), x.stride(0), nullptr, 0, bf16_ptr(w), bf16_ptr(b), bf16_mut(y), nullptr,
-                               mean.data_ptr<float>(), rstd.data_ptr<float>(), H, (float)eps, 256, 1.f, nullptr));
+  if (T == 0) return {y, h, mean, rstd};
+  const int per = norm::pick_per(H);
+  if (!ADD) launch_layernorm_fwd<0>(per, x, res, w, b, y, h, mean, rstd, T, H, eps, d);
+  else if (d.rng == nullptr) launch_layernorm_fwd<1>(per, x, res, w, b, y, h, mean, rstd, T, H, eps, d);
+  else launch_layernorm_fwd<2>(per, x, res, w, b, y, h, mean, rstd, T, H, eps, d);
   DTG_LAUNCH_CHECK();
+  return {y, h, mean, rstd};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> layernorm_fwd(const at::Tensor& x, const at::Tensor& w,
+                                                             const at::Tensor& b, double eps) {
+  auto [y, h, mean, rstd] = layernorm_fwd_impl<false>(x, at::Tensor(), w, b, eps, 0.0, c10::nullopt);
   return {y, mean, rstd};
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> dropout_add_layernorm_fwd(
     const at::Tensor& x, const at::Tensor& res, const at::Tensor& w, const at::Tensor& b, double eps, double p,
     const c10::optional<at::Tensor>& rng) {
-  ln::check_rows(x, "x");
-  ln::check_rows(res, "residual");
-  const int T = x.size(0), H = x.size(1);
-  DTG_CHECK(res.size(0) == T && res.size(1) == H, "dropout_add_layernorm: shape mismatch");
-  ln::check_affine(w, &b, H);
-  const ln::Drop d = ln::make_drop(p, rng, x);
-  const c10::DeviceGuard g(x.device());
-  auto y = at::empty({T, H}, x.options());
-  auto h = at::empty({T, H}, x.options());
-  auto mean = at::empty({T}, x.options().dtype(at::kFloat));
-  auto rstd = at::empty({T}, x.options().dtype(at::kFloat));
-  if (T == 0) return {y, h, mean, rstd};
-  const int per = ln::pick_per(H);
-  if (d.rng != nullptr) {
-    DTG_LN_PER_DISPATCH(per, ln::layernorm_fwd_kernel<P, 2><<<T, ln::kThreads, 0, stream()>>>(
-                                 bf16_ptr(x), x.stride(0), bf16_ptr(res), res.stride(0), bf16_ptr(w), bf16_ptr(b),
-                                 bf16_mut(y), bf16_mut(h), mean.data_ptr<float>(), rstd.data_ptr<float>(), H,
-                                 (float)eps, d.thr, d.scale, d.rng));
-  } else {
-    DTG_LN_PER_DISPATCH(per, ln::layernorm_fwd_kernel<P, 1><<<T, ln::kThreads, 0, stream()>>>(
-                                 bf16_ptr(x), x.stride(0), bf16_ptr(res), res.stride(0), bf16_ptr(w), bf16_ptr(b),
-                                 bf16_mut(y), bf16_mut(h), mean.data_ptr<float>(), rstd.data_ptr<float>(), H,
-                                 (float)eps, 256, 1.f, nullptr));
-  }
-  DTG_LAUNCH_CHECK();
-  return {y, h, mean, rstd};
+  return layernorm_fwd_impl<true>(x, res, w, b, eps, p, rng);
 }
 
 template <bool DRES, bool DROP>
-static void launch_layernorm_bwd(int per, int nb, const at::Tensor& dy, const at::Tensor& h, const at::Tensor& w,
-                                 const at::Tensor& mean, const at::Tensor& rstd, const at::Tensor& dres,
-                                 at::Tensor& dh, at::Tensor& dx, at::Tensor& part, int T, int H, int rpb,
+static void launch_layernorm_bwd(int per, const norm::Split& s, const at::Tensor& dy, const at::Tensor& h,
+                                 const at::Tensor& w, const at::Tensor& mean, const at::Tensor& rstd,
+                                 const at::Tensor& dres, at::Tensor& dh, at::Tensor& dx, at::Tensor& part, int T, int H,
                                  const ln::Drop& d) {
   float* dw_part = part.data_ptr<float>();
-  DTG_LN_PER_DISPATCH(per, ln::layernorm_bwd_kernel<P, DRES, DROP><<<nb, ln::kThreads, 0, stream()>>>(
-                               bf16_ptr(dy), bf16_ptr(h), h.stride(0), bf16_ptr(w), mean.data_ptr<float>(),
-                               rstd.data_ptr<float>(), DRES ? bf16_ptr(dres) : nullptr, bf16_mut(dh),
-                               DROP ? bf16_mut(dx) : nullptr, dw_part, dw_part + (int64_t)nb * H, T, H, rpb, d.thr,
-                               d.scale, d.rng));
+  DTG_PER_DISPATCH("layernorm", per,
+                   ln::layernorm_bwd_kernel<P, DRES, DROP><<<(unsigned)s.n_blocks, ln::kThreads, 0, stream()>>>(
+                       bf16_ptr(dy), bf16_ptr(h), h.stride(0), bf16_ptr(w), mean.data_ptr<float>(),
+                       rstd.data_ptr<float>(), DRES ? bf16_ptr(dres) : nullptr, bf16_mut(dh),
+                       DROP ? bf16_mut(dx) : nullptr, dw_part, dw_part + s.n_blocks * H, T, H, (int)s.per_block, d.thr,
+                       d.scale, d.rng));
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> layernorm_bwd(
     const at::Tensor& dy_, const at::Tensor& h, const at::Tensor& w, const at::Tensor& mean, const at::Tensor& rstd,
     const c10::optional<at::Tensor>& dres_, double p, const c10::optional<at::Tensor>& rng) {
   auto dy = dy_.contiguous();
-  ln::check_rows(h, "h");
+  norm::check_rows(h, "h");
   DTG_CHECK_CUDA_BF16(dy);
   const int T = h.size(0), H = h.size(1);
   ln::check_affine(w, nullptr, H);
   DTG_CHECK(dy.dim() == 2 && dy.size(0) == T && dy.size(1) == H, "layernorm_bwd: dy shape");
-  DTG_CHECK(mean.is_cuda() && mean.scalar_type() == at::kFloat && mean.numel() == T && mean.is_contiguous(),
-            "layernorm_bwd: mean");
-  DTG_CHECK(rstd.is_cuda() && rstd.scalar_type() == at::kFloat && rstd.numel() == T && rstd.is_contiguous(),
-            "layernorm_bwd: rstd");
+  norm::check_stat(mean, T, "layernorm_bwd: mean");
+  norm::check_stat(rstd, T, "layernorm_bwd: rstd");
   const ln::Drop d = ln::make_drop(p, rng, h);
   const bool drop = d.rng != nullptr;
   const c10::DeviceGuard g(h.device());
@@ -404,28 +332,18 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> layernorm_bwd(
     dwb.zero_();
     return {dh, dx, dwb.select(0, 0), dwb.select(0, 1)};
   }
-  at::Tensor dres;
-  const bool has_dres = dres_.has_value() && dres_->defined();
-  if (has_dres) {
-    dres = dres_->contiguous();
-    DTG_CHECK_CUDA_BF16(dres);
-    DTG_CHECK(dres.dim() == 2 && dres.size(0) == T && dres.size(1) == H, "layernorm_bwd: dres shape");
-  }
-  const int per = ln::pick_per(H);
+  const at::Tensor dres = norm::checked_dres(dres_, T, H, "layernorm_bwd: dres shape");
+  const bool has_dres = dres.defined();
+  const int per = norm::pick_per(H);
   DTG_CHECK(per > 0, "layernorm: unsupported hidden size");
-  // the block count of rmsnorm_bwd: ~2 workgroups per CU keeps the partial matrices small
-  const int nblk = std::min(T, 512);
-  const int rpb = (T + nblk - 1) / nblk;
-  const int nb = (T + rpb - 1) / rpb;
-  auto part = at::empty({2, nb, H}, h.options().dtype(at::kFloat));
-  if (has_dres && drop) launch_layernorm_bwd<true, true>(per, nb, dy, h, w, mean, rstd, dres, dh, dx, part, T, H, rpb, d);
-  else if (has_dres) launch_layernorm_bwd<true, false>(per, nb, dy, h, w, mean, rstd, dres, dh, dx, part, T, H, rpb, d);
-  else if (drop) launch_layernorm_bwd<false, true>(per, nb, dy, h, w, mean, rstd, dres, dh, dx, part, T, H, rpb, d);
-  else launch_layernorm_bwd<false, false>(per, nb, dy, h, w, mean, rstd, dres, dh, dx, part, T, H, rpb, d);
+  const norm::Split s = norm::row_bwd_split(T);
+  auto part = at::empty({2, s.n_blocks, H}, h.options().dtype(at::kFloat));  // dw partials, then db partials
+  if (has_dres && drop) launch_layernorm_bwd<true, true>(per, s, dy, h, w, mean, rstd, dres, dh, dx, part, T, H, d);
+  else if (has_dres) launch_layernorm_bwd<true, false>(per, s, dy, h, w, mean, rstd, dres, dh, dx, part, T, H, d);
+  else if (drop) launch_layernorm_bwd<false, true>(per, s, dy, h, w, mean, rstd, dres, dh, dx, part, T, H, d);
+  else launch_layernorm_bwd<false, false>(per, s, dy, h, w, mean, rstd, dres, dh, dx, part, T, H, d);
   DTG_LAUNCH_CHECK();
-  ln::colsum2_to_bf16_kernel<<<dim3((H + ln::kColsumCols - 1) / ln::kColsumCols, 2), 256, 0, stream()>>>(
-      part.data_ptr<float>(), nb, H, bf16_mut(dwb));
-  DTG_LAUNCH_CHECK();
+  norm::colsum_to_bf16(part.data_ptr<float>(), 2, (int)s.n_blocks, H, bf16_mut(dwb));
   return {dh, dx, dwb.select(0, 0), dwb.select(0, 1)};
 }
 

@@ -12,20 +12,16 @@
 //   dx = rstd * (w*dy - xh * mean(w*dy*xh)),  xh = x * rstd,   dw[q|k][D] = sum over tokens and heads dy * xh.
 // rstd (f32 [T, nq + nkv]) is SAVED by the forward and read here, not recomputed: 4 B per head against
 // the 2 * 2 * D B the backward streams anyway, and the backward keeps a single group reduction.
-// dw goes through per-workgroup f32 partials and a fixed-order column sum (as rmsnorm.hip /
-// layernorm.hip): no atomics, bitwise reproducible for a given shape.
+// dw goes through per-workgroup f32 partials and the fixed-order column sum of norm_common.h (as
+// rmsnorm.hip / layernorm.hip): no atomics, bitwise reproducible for a given shape.
 //
 // Layout: a head is D/16 lanes (8 at D = 128, 4 at D = 64); a lane owns 8 elements of the first half
 // and the matching 8 of the second half (two 16-B accesses), so the rotation is lane-local and the
 // mean is a 3- or 2-step sub-wave butterfly.  A wave therefore carries 8 (16) heads.  ROPE = false
 // is the norm-only form (empty tables), used before the Ulysses all-to-all.
-#include "common.h"
+#include "norm_common.h"
 
 namespace dtg {
-
-constexpr int kQkThreads = 256;
-constexpr int kQkMaxBlocks = 1024;  // backward workgroups = rows of the dw partial matrix
-constexpr int kQkColsumCols = 16;
 
 template <int G>
 __device__ __forceinline__ float group_sum(float v) {
@@ -47,14 +43,14 @@ __device__ __forceinline__ void widen8(const u16x8& v, float* out) {
 
 // One lane group per (token, head); every lane reaches the butterfly (lanes past the end carry zeros).
 template <int D, bool ROPE>
-__global__ __launch_bounds__(kQkThreads) void qk_norm_rope_fwd_kernel(
+__global__ __launch_bounds__(norm::kThreads) void qk_norm_rope_fwd_kernel(
     uint16_t* __restrict__ qkv, int64_t row_stride, const uint16_t* __restrict__ wq,
     const uint16_t* __restrict__ wk, const float* __restrict__ cos_t, const float* __restrict__ sin_t,
     const int64_t* __restrict__ pos, uint16_t* __restrict__ xqk, float* __restrict__ rstd_out, int nq, int nh,
     int64_t T, float eps) {
   constexpr int HALF = D / 2;
   constexpr int GROUPS = HALF / 8;
-  const int64_t gid = (int64_t)blockIdx.x * kQkThreads + threadIdx.x;
+  const int64_t gid = (int64_t)blockIdx.x * norm::kThreads + threadIdx.x;
   const bool valid = gid < T * nh * GROUPS;
   const int grp = gid % GROUPS;
   const int64_t th = gid / GROUPS;
@@ -112,14 +108,14 @@ __global__ __launch_bounds__(kQkThreads) void qk_norm_rope_fwd_kernel(
 // summed over the lane groups through LDS in a fixed order and written as one row of `part`
 // [gridDim.x, 2 * D] (q columns, then k columns).
 template <int D, bool ROPE>
-__global__ __launch_bounds__(kQkThreads) void qk_norm_rope_bwd_kernel(
+__global__ __launch_bounds__(norm::kThreads) void qk_norm_rope_bwd_kernel(
     uint16_t* __restrict__ dqkv, int64_t row_stride, const uint16_t* __restrict__ xqk,
     const float* __restrict__ rstd_in, const uint16_t* __restrict__ wq, const uint16_t* __restrict__ wk,
     const float* __restrict__ cos_t, const float* __restrict__ sin_t, const int64_t* __restrict__ pos,
     float* __restrict__ part, int nq, int nh, int64_t T, int tok_per_block) {
   constexpr int HALF = D / 2;
   constexpr int GROUPS = HALF / 8;
-  constexpr int SLOTS = kQkThreads / GROUPS;
+  constexpr int SLOTS = norm::kThreads / GROUPS;
   __shared__ float red[2][SLOTS][D];
   const int slot = threadIdx.x / GROUPS, grp = threadIdx.x % GROUPS;
   const int64_t t0 = (int64_t)blockIdx.x * tok_per_block;
@@ -207,32 +203,11 @@ __global__ __launch_bounds__(kQkThreads) void qk_norm_rope_bwd_kernel(
     red[1][slot][HALF + grp * 8 + j] = acck[8 + j];
   }
   __syncthreads();
-  for (int c = threadIdx.x; c < 2 * D; c += kQkThreads) {
+  for (int c = threadIdx.x; c < 2 * D; c += norm::kThreads) {
     const int kind = c / D, col = c % D;
     float t = 0.f;
     for (int s = 0; s < SLOTS; ++s) t += red[kind][s][col];
     part[(int64_t)blockIdx.x * (2 * D) + c] = t;
-  }
-}
-
-// Column sums of the [nrows, W] f32 partials in a fixed order -> bf16 [W]: 16 columns x 16 row groups
-// per workgroup, the row groups combined through LDS (the shape of rmsnorm.hip's colsum).
-__global__ __launch_bounds__(256) void qk_colsum_to_bf16_kernel(const float* __restrict__ part, int nrows, int W,
-                                                                uint16_t* __restrict__ out) {
-  constexpr int G = 256 / kQkColsumCols;
-  __shared__ float red[G][kQkColsumCols + 1];
-  const int lane = threadIdx.x % kQkColsumCols, grp = threadIdx.x / kQkColsumCols;
-  const int c = blockIdx.x * kQkColsumCols + lane;
-  float s = 0.f;
-  if (c < W)
-    for (int r = grp; r < nrows; r += G) s += part[(int64_t)r * W + c];
-  red[grp][lane] = s;
-  __syncthreads();
-  if (grp == 0 && c < W) {
-    float t = 0.f;
-#pragma unroll
-    for (int g = 0; g < G; ++g) t += red[g][lane];
-    out[c] = f2bf(t);
   }
 }
 
@@ -287,13 +262,13 @@ std::tuple<at::Tensor, at::Tensor> qk_norm_rope_fwd_(const at::Tensor& qkv, cons
   auto rstd = at::empty({T, nh}, qkv.options().dtype(at::kFloat));
   if (T == 0) return {xqk, rstd};
   const int64_t total = T * nh * (head_dim / 16);
-  const int64_t nblk = (total + kQkThreads - 1) / kQkThreads;
+  const int64_t nblk = (total + norm::kThreads - 1) / norm::kThreads;
   DTG_CHECK(nblk < (int64_t(1) << 31), "qk_norm_rope_fwd_: too many tokens");
   const float* cp = rope ? cos_t.data_ptr<float>() : nullptr;
   const float* sp = rope ? sin_t.data_ptr<float>() : nullptr;
   const int64_t* pp = rope ? pos.data_ptr<int64_t>() : nullptr;
   DTG_QK_DISPATCH(head_dim, rope,
-                  qk_norm_rope_fwd_kernel<HD, RP><<<(unsigned)nblk, kQkThreads, 0, stream()>>>(
+                  qk_norm_rope_fwd_kernel<HD, RP><<<(unsigned)nblk, norm::kThreads, 0, stream()>>>(
                       bf16_mut(qkv), qkv.stride(0), bf16_ptr(wq), bf16_ptr(wk), cp, sp, pp, bf16_mut(xqk),
                       rstd.data_ptr<float>(), (int)nq, (int)nh, T, (float)eps));
   DTG_LAUNCH_CHECK();
@@ -310,29 +285,26 @@ std::tuple<at::Tensor, at::Tensor> qk_norm_rope_bwd_(const at::Tensor& dqkv, con
   DTG_CHECK_CUDA_BF16(xqk);
   DTG_CHECK(xqk.dim() == 2 && xqk.is_contiguous() && xqk.size(0) == T && xqk.size(1) == nh * D,
             "qk_norm_rope_bwd_: xqk must be contiguous [T, (nq + nkv) * head_dim]");
-  DTG_CHECK(rstd.is_cuda() && rstd.scalar_type() == at::kFloat && rstd.is_contiguous() && rstd.numel() == T * nh,
-            "qk_norm_rope_bwd_: rstd must be f32 [T, nq + nkv]");
+  norm::check_stat(rstd, T * nh, "qk_norm_rope_bwd_: rstd must be f32 [T, nq + nkv]");
   const c10::DeviceGuard g(dqkv.device());
   auto dw = at::empty({2 * D}, wq.options());
   if (T == 0) {
     dw.zero_();
     return {dw.narrow(0, 0, D), dw.narrow(0, D, D)};
   }
-  const int64_t tpb = (T + kQkMaxBlocks - 1) / kQkMaxBlocks;
-  const int64_t nb = (T + tpb - 1) / tpb;
+  const norm::Split s = norm::qk_bwd_split(T);
+  const int64_t tpb = s.per_block, nb = s.n_blocks;
   DTG_CHECK(tpb * nh < (int64_t(1) << 30), "qk_norm_rope_bwd_: too many tokens");
   auto part = at::empty({nb, 2 * D}, dqkv.options().dtype(at::kFloat));
   const float* cp = rope ? cos_t.data_ptr<float>() : nullptr;
   const float* sp = rope ? sin_t.data_ptr<float>() : nullptr;
   const int64_t* pp = rope ? pos.data_ptr<int64_t>() : nullptr;
   DTG_QK_DISPATCH(head_dim, rope,
-                  qk_norm_rope_bwd_kernel<HD, RP><<<(unsigned)nb, kQkThreads, 0, stream()>>>(
+                  qk_norm_rope_bwd_kernel<HD, RP><<<(unsigned)nb, norm::kThreads, 0, stream()>>>(
                       bf16_mut(dqkv), dqkv.stride(0), bf16_ptr(xqk), rstd.data_ptr<float>(), bf16_ptr(wq),
                       bf16_ptr(wk), cp, sp, pp, part.data_ptr<float>(), (int)nq, (int)nh, T, (int)tpb));
   DTG_LAUNCH_CHECK();
-  qk_colsum_to_bf16_kernel<<<(unsigned)((2 * D + kQkColsumCols - 1) / kQkColsumCols), 256, 0, stream()>>>(
-      part.data_ptr<float>(), (int)nb, (int)(2 * D), bf16_mut(dw));
-  DTG_LAUNCH_CHECK();
+  norm::colsum_to_bf16(part.data_ptr<float>(), 1, (int)nb, (int)(2 * D), bf16_mut(dw));
   return {dw.narrow(0, 0, D), dw.narrow(0, D, D)};
 }
 

@@ -411,7 +411,7 @@ def ln_dropout_keep(seed, offset, T, H, p):
 
 
 def _ln_check_rows(t, name):
-    """check_rows of layernorm.hip: 2-D, unit inner stride, 16-B aligned rows, H % 8 == 0."""
+    """check_rows of norm_common.h as layernorm.hip uses it: 2-D, unit inner stride, 16-B aligned rows, H % 8 == 0."""
     if not (t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0):
         raise RuntimeError(f"dtg: {name} must be 2-D with unit inner stride and 16-byte aligned rows")
     if t.shape[1] % 8:

@@ -34,6 +34,21 @@ def test_rmsnorm_unsupported_hidden_size(cuda):
         dops.rmsnorm_bwd(x, x, w, torch.ones(5, device=cuda), None)
 
 
+def test_rmsnorm_bwd_refuses_bad_dres_and_rstd(cuda):
+    """A dres that is not [T, H] and an rstd the device cannot read are refused on the host (they
+    used to go straight into the kernel)."""
+    T, H = 5, 64
+    x = torch.zeros(T, H, dtype=BF, device=cuda)
+    w = torch.ones(H, dtype=BF, device=cuda)
+    rstd = torch.ones(T, device=cuda)
+    with pytest.raises(RuntimeError, match="dres shape"):
+        dops.rmsnorm_bwd(x, x, w, rstd, torch.zeros(T, H + 8, dtype=BF, device=cuda))
+    with pytest.raises(RuntimeError, match="dres shape"):
+        dops.rmsnorm_bwd(x, x, w, rstd, torch.zeros(T * H, dtype=BF, device=cuda))
+    with pytest.raises(RuntimeError, match="rmsnorm_bwd: rstd"):
+        dops.rmsnorm_bwd(x, x, w, torch.ones(T), None)
+
+
 @pytest.mark.parametrize("with_dres", [True, False])
 @pytest.mark.parametrize("T", C.RMS_BWD_T)
 def test_rmsnorm_bwd_rows(cuda, T, with_dres):
