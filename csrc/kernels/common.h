@@ -141,6 +141,24 @@ __device__ __forceinline__ void transpose8x8(u16x8 (&v)[8]) {
   }
 }
 
+// LDS staging of the tile-transposing kernels.  A tile of 16-bit values with an even pitch P
+// (tile width + 2 halfwords); rows go in as four dwords, columns come out as eight halfwords
+// from consecutive rows.  `col` of lds_put8 is a multiple of 8.
+template <int P>
+__device__ __forceinline__ void lds_put8(uint16_t* tile, int row, int col, u16x8 v) {
+  uint32_t* d = reinterpret_cast<uint32_t*>(tile + row * P + col);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) d[j] = (uint32_t)v[2 * j] | ((uint32_t)v[2 * j + 1] << 16);
+}
+
+template <int P>
+__device__ __forceinline__ u16x8 lds_col8(const uint16_t* tile, int row, int col) {
+  u16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = tile[(row + j) * P + col];
+  return v;
+}
+
 // Grid of the tile-transposing streaming kernels: blockIdx.x = column tile (fastest, so the
 // workgroups resident at one time read neighbouring segments of the same source rows),
 // blockIdx.y = row tile.  A banded 1-D tile walk (column tiles grouped so that the transposed

@@ -79,9 +79,7 @@ __global__ __launch_bounds__(256) void transpose_mats_kernel(const uint16_t* __r
     const int64_t r = r0 + lr, c = c0 + lc;
     u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
     if (r < m.rows && c < m.cols) v = *reinterpret_cast<const u16x8*>(src + r * m.cols + c);
-    uint32_t* d = reinterpret_cast<uint32_t*>(tile + lr * P + lc);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) d[j] = (uint32_t)v[2 * j] | ((uint32_t)v[2 * j + 1] << 16);
+    lds_put8<P>(tile, lr, lc, v);
   }
   __syncthreads();
 #pragma unroll
@@ -89,9 +87,7 @@ __global__ __launch_bounds__(256) void transpose_mats_kernel(const uint16_t* __r
     const int id = tid + 256 * i;
     const int oc = id / VPC, orr = (id % VPC) * 8;
     const int64_t c = c0 + oc, r = r0 + orr;
-    u16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = tile[(orr + j) * P + oc];
+    const u16x8 v = lds_col8<P>(tile, orr, oc);
     if (c < m.cols && r < m.rows) *reinterpret_cast<u16x8*>(dst + c * m.rows + r) = v;
   }
 }

@@ -590,6 +590,12 @@ def flash_attn_bwd_qkv_rope(dout, qkv, nq, nkv, head_dim, o, lse, cu_seqlens, ma
 
 
 def swiglu_bwd_t(dh, gu):
+    """check_x / check_dh of csrc/kernels/mlp_act.h, then the two untiled operators."""
+    if not (gu.dim() == 2 and gu.stride(1) == 1 and gu.stride(0) % 8 == 0 and gu.shape[1] % 16 == 0):
+        raise RuntimeError("dtg: swiglu_bwd_t: the pre-activation must be [T, 2 * I] with unit inner stride, "
+                           "16-byte aligned rows and I % 8 == 0")
+    if not (dh.dim() == 2 and dh.shape[0] == gu.shape[0] and dh.shape[1] == gu.shape[1] // 2):
+        raise RuntimeError("dtg: swiglu_bwd_t: shape mismatch")
     dgu = swiglu_bwd(dh, gu)
     return dgu, dgu.t().contiguous(), swiglu_fwd(gu).t().contiguous()
 

@@ -59,6 +59,32 @@ def _bwd_layout(x, w):
     return True, w.shape[0] >= w.shape[1]
 
 
+def _bias_grad(b, dy):
+    """b's gradient: the f32 column sum of dy, rounded once."""
+    return route_param_grad(b, dy.sum(0, dtype=torch.float32).to(dy.dtype))
+
+
+def _dx_mm(dy, w, tn):
+    """dX = dy @ w, from the K-contiguous W^T when `tn`."""
+    return torch.mm(dy, _wt(w).t()) if tn else torch.mm(dy, w)
+
+
+def _dw_mm(w, dy, x, tn, dy_t=None, x_t=None):
+    """w's gradient dy^T @ x; when `tn`, from token-contiguous operands (dy_t / x_t where the
+    caller has them, else transposed here)."""
+    if not (tn and _tn_ok(dy)):
+        return route_weight_grad_mm(w, dy, x)
+    return route_weight_grad_mm(w, dy, x, a_t=ops.transpose2d(dy) if dy_t is None else dy_t,
+                                b_t=ops.transpose2d(x) if x_t is None else x_t)
+
+
+def _linear_backward(ctx, dy, x, w):
+    dx_tn, dw_tn = _bwd_layout(x, w)
+    dx = _dx_mm(dy, w, dx_tn) if ctx.needs_input_grad[0] else None
+    dw = _dw_mm(w, dy, x, dw_tn) if ctx.needs_input_grad[1] else None
+    return dx, dw
+
+
 class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, out=None):
@@ -70,16 +96,7 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        dx_tn, dw_tn = _bwd_layout(x, w)
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.mm(dy, _wt(w).t()) if dx_tn else torch.mm(dy, w)
-        if ctx.needs_input_grad[1]:
-            if dw_tn and _tn_ok(dy):
-                dw = route_weight_grad_mm(w, dy, x, a_t=ops.transpose2d(dy), b_t=ops.transpose2d(x))
-            else:
-                dw = route_weight_grad_mm(w, dy, x)
-        return dx, dw, None
+        return (*_linear_backward(ctx, dy, x, w), None)
 
 
 def linear(x, w, b=None, out=None):
@@ -100,18 +117,8 @@ class _LinearBias(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, b = ctx.saved_tensors
-        dx_tn, dw_tn = _bwd_layout(x, w)
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.mm(dy, _wt(w).t()) if dx_tn else torch.mm(dy, w)
-        if ctx.needs_input_grad[1]:
-            if dw_tn and _tn_ok(dy):
-                dw = route_weight_grad_mm(w, dy, x, a_t=ops.transpose2d(dy), b_t=ops.transpose2d(x))
-            else:
-                dw = route_weight_grad_mm(w, dy, x)
-        if ctx.needs_input_grad[2]:
-            db = route_param_grad(b, dy.sum(0, dtype=torch.float32).to(dy.dtype))
-        return dx, dw, db
+        dx, dw = _linear_backward(ctx, dy, x, w)
+        return dx, dw, _bias_grad(b, dy) if ctx.needs_input_grad[2] else None
 
 
 # --------------------------------------------------------------------------------------------
@@ -503,13 +510,41 @@ def swiglu(gu):
     return _SwiGLU.apply(gu)
 
 
-class _SwiGLUMLP(torch.autograd.Function):
-    """down(swiglu(x @ W_gu^T)) as one autograd node.
+def _mlp_backward(act, x, w1, w2, a, dy, b1=None, b2=None):
+    """Backward of y = act(x @ w1^T (+ b1)) @ w2^T (+ b2) from the saved pre-activation a; `act`
+    names the operators {act}_fwd / _bwd / _bwd_t.  Returns dx, dw1, dw2, db1, db2.
 
-    Saves only x and gu (h = silu(g)*u is recomputed in backward, [T, I] less resident per
-    layer).  On the TN path the backward's SwiGLU kernel writes dgu together with dgu^T and h^T,
-    the token-contiguous operands of the two weight-gradient GEMMs, so neither needs a separate
-    transpose pass; dX GEMMs use transposed weight copies (see _bwd_layout)."""
+    h = act(a) is recomputed.  On the TN path the {act}_bwd_t kernel writes da together with da^T
+    and h^T, the token-contiguous operands of the two weight-gradient GEMMs, so neither needs a
+    separate transpose pass; the dX GEMMs use transposed weight copies (see _bwd_layout).  The
+    parameters are routed in the order b2, w2, b1, w1 (the engines count notifications per bucket),
+    and dh, h^T and h are dropped as soon as they are spent: they set the peak memory."""
+    dy = dy.contiguous()
+    dx_tn, dw_tn = _bwd_layout(x, w1)
+    fused = dw_tn and _tn_ok(dy, a) and a.stride(0) == a.shape[1]
+    db2 = None if b2 is None else _bias_grad(b2, dy)
+    dh = _dx_mm(dy, w2, dx_tn)
+    if fused:
+        da, da_t, h_t = getattr(ops, act + "_bwd_t")(dh, a)
+        del dh
+        dw2 = _dw_mm(w2, dy, None, True, x_t=h_t)
+        del h_t
+    else:
+        da_t = None
+        h = getattr(ops, act + "_fwd")(a)
+        da = getattr(ops, act + "_bwd")(dh, a)
+        del dh
+        dw2 = _dw_mm(w2, dy, h, False)
+        del h
+    db1 = None if b1 is None else _bias_grad(b1, da)
+    dx = _dx_mm(da, w1, dx_tn)
+    dw1 = _dw_mm(w1, da, x, fused, dy_t=da_t)
+    return dx, dw1, dw2, db1, db2
+
+
+class _SwiGLUMLP(torch.autograd.Function):
+    """down(swiglu(x @ W_gu^T)) as one autograd node.  Saves only x and gu
+    ([T, I] less resident per layer than with h); the backward is _mlp_backward."""
 
     @staticmethod
     def forward(ctx, x, w_gu, w_down, out=None):
@@ -523,26 +558,7 @@ class _SwiGLUMLP(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w_gu, w_down, gu = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx_tn, dw_tn = _bwd_layout(x, w_gu)
-        fused = dw_tn and _tn_ok(dy, gu) and gu.stride(0) == gu.shape[1]
-        dh = torch.mm(dy, _wt(w_down).t()) if dx_tn else torch.mm(dy, w_down)
-        if fused:
-            dgu, dgu_t, h_t = ops.swiglu_bwd_t(dh, gu)
-            del dh
-            dw_down = route_weight_grad_mm(w_down, dy, None, a_t=ops.transpose2d(dy), b_t=h_t)
-            del h_t
-        else:
-            h = ops.swiglu_fwd(gu)
-            dgu = ops.swiglu_bwd(dh, gu)
-            del dh
-            dw_down = route_weight_grad_mm(w_down, dy, h)
-            del h
-        dx = torch.mm(dgu, _wt(w_gu).t()) if dx_tn else torch.mm(dgu, w_gu)
-        if fused:
-            dw_gu = route_weight_grad_mm(w_gu, dgu, x, a_t=dgu_t, b_t=ops.transpose2d(x))
-        else:
-            dw_gu = route_weight_grad_mm(w_gu, dgu, x)
+        dx, dw_gu, dw_down, _, _ = _mlp_backward("swiglu", x, w_gu, w_down, gu, dy)
         return dx, dw_gu, dw_down, None
 
 
@@ -556,12 +572,9 @@ def swiglu_mlp(x, w_gu, w_down, out=None):
 # GELU MLP (GPT-2)
 # --------------------------------------------------------------------------------------------
 class _GeluMLP(torch.autograd.Function):
-    """proj(gelu_tanh(x @ W_fc^T + b_fc)) + b_proj as one autograd node, shaped like _SwiGLUMLP.
-
-    Saves x and the pre-activation a (h = gelu(a) is recomputed in backward).  On the TN path the
-    backward's GELU kernel writes da together with da^T and h^T, the token-contiguous operands
-    of the two weight-gradient GEMMs, so the transposes _LinearBias would spend around the GELU
-    never run.  The bias gradients are f32 column sums as in _LinearBias."""
+    """proj(gelu_tanh(x @ W_fc^T + b_fc)) + b_proj as one autograd node.  Saves x and the
+    pre-activation a; the backward is _mlp_backward, so the transposes _LinearBias would spend
+    around the GELU never run.  The bias gradients are f32 column sums as in _LinearBias."""
 
     @staticmethod
     def forward(ctx, x, w_fc, b_fc, w_proj, b_proj):
@@ -573,28 +586,7 @@ class _GeluMLP(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w_fc, b_fc, w_proj, b_proj, a = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx_tn, dw_tn = _bwd_layout(x, w_fc)
-        fused = dw_tn and _tn_ok(dy, a) and a.stride(0) == a.shape[1]
-        db_proj = route_param_grad(b_proj, dy.sum(0, dtype=torch.float32).to(dy.dtype))
-        dh = torch.mm(dy, _wt(w_proj).t()) if dx_tn else torch.mm(dy, w_proj)
-        if fused:
-            da, da_t, h_t = ops.gelu_bwd_t(dh, a)
-            del dh
-            dw_proj = route_weight_grad_mm(w_proj, dy, None, a_t=ops.transpose2d(dy), b_t=h_t)
-            del h_t
-        else:
-            h = ops.gelu_fwd(a)
-            da = ops.gelu_bwd(dh, a)
-            del dh
-            dw_proj = route_weight_grad_mm(w_proj, dy, h)
-            del h
-        db_fc = route_param_grad(b_fc, da.sum(0, dtype=torch.float32).to(da.dtype))
-        dx = torch.mm(da, _wt(w_fc).t()) if dx_tn else torch.mm(da, w_fc)
-        if fused:
-            dw_fc = route_weight_grad_mm(w_fc, da, x, a_t=da_t, b_t=ops.transpose2d(x))
-        else:
-            dw_fc = route_weight_grad_mm(w_fc, da, x)
+        dx, dw_fc, dw_proj, db_fc, db_proj = _mlp_backward("gelu", x, w_fc, w_proj, a, dy, b_fc, b_proj)
         return dx, dw_fc, db_fc, dw_proj, db_proj
 
 

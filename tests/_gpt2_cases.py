@@ -389,8 +389,12 @@ def check_gelu(dev, T, I):
 
 def check_gelu_bwd_t(dev, T, I):
     x, dh = gelu_inputs(T, I)
-    dx, dx_t, h_t = dops.gelu_bwd_t(dh.to(dev), _strided(x, dev))
+    xs = _strided(x, dev)
+    dx, dx_t, h_t = dops.gelu_bwd_t(dh.to(dev), xs)
     assert dx.shape == (T, I) and dx_t.shape == (I, T) and h_t.shape == (I, T)
+    # one functor behind the tiled and the untiled kernels: the same bits
+    assert torch.equal(dx, dops.gelu_bwd(dh.to(dev), xs)), "gelu_bwd_t: dx != gelu_bwd"
+    assert torch.equal(h_t.t(), dops.gelu_fwd(xs)), "gelu_bwd_t: h_t.t() != gelu_fwd"
     R.assert_within(dx, gelu_bwd_ref(dh, x), gelu_bwd_term(dh, x), "gelu_bwd_t dx")
     assert torch.equal(dx_t, dx.t()), "gelu_bwd_t: dx_t != dx.t()"
     R.assert_within(h_t.t(), gelu_ref(x), gelu_term(x), "gelu_bwd_t h_t")

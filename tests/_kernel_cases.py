@@ -3,6 +3,7 @@ test_kernel_refs_cpu.py (the package's f32 CPU ops): the same inputs, the same f
 and the same bounds (tests/_refs.py), on whichever device `dev` names.  Inputs are generated on the
 CPU from fixed seeds.
 """
+import pytest
 import torch
 
 import dtg  # noqa: F401
@@ -252,11 +253,30 @@ def check_swiglu(dev, T, I):
 
 def check_swiglu_bwd_t(dev, T, I):
     gu, dh = swiglu_inputs(T, I)
-    dgu, dgu_t, h_t = dops.swiglu_bwd_t(dh.to(dev), _strided_gu(gu, dev))
+    gs = _strided_gu(gu, dev)
+    dgu, dgu_t, h_t = dops.swiglu_bwd_t(dh.to(dev), gs)
     assert dgu.shape == (T, 2 * I) and dgu_t.shape == (2 * I, T) and h_t.shape == (I, T)
+    # one functor behind the tiled and the untiled kernels: the same bits
+    assert torch.equal(dgu, dops.swiglu_bwd(dh.to(dev), gs)), "swiglu_bwd_t: dgu != swiglu_bwd"
+    assert torch.equal(h_t.t(), dops.swiglu_fwd(gs)), "swiglu_bwd_t: h_t.t() != swiglu_fwd"
     R.assert_within(dgu, R.swiglu_bwd_ref(dh, gu), R.swiglu_bwd_term(dh, gu), "swiglu_bwd_t dgu")
     assert torch.equal(dgu_t, dgu.t()), "swiglu_bwd_t: dgu_t != dgu.t()"
     R.assert_within(h_t.t(), R.swiglu_ref(gu), R.swiglu_term(gu), "swiglu_bwd_t h_t")
+
+
+def check_swiglu_bwd_t_refusals(dev):
+    """gu widths 24 (I = 12) and 33 (2I + 1, in rows of 40 so that only the width is wrong), and a
+    dh of the right size that is not [T, I]."""
+    odd = torch.zeros(8, 24, dtype=BF, device=dev)
+    plus1 = torch.zeros(8, 40, dtype=BF, device=dev)[:, :33]
+    assert plus1.stride(0) % 8 == 0 and plus1.stride(1) == 1
+    for gu in (odd, plus1):
+        with pytest.raises(RuntimeError, match="swiglu_bwd_t"):
+            dops.swiglu_bwd_t(torch.zeros(8, gu.size(1) // 2, dtype=BF, device=dev), gu)
+    gu = torch.zeros(8, 32, dtype=BF, device=dev)
+    for shape in ((8 * 16,), (8, 16, 1), (16, 8)):
+        with pytest.raises(RuntimeError, match="swiglu_bwd_t"):
+            dops.swiglu_bwd_t(torch.zeros(shape, dtype=BF, device=dev), gu)
 
 
 def check_swiglu_empty(dev):

@@ -151,6 +151,19 @@ def test_gelu_mlp_tn_path_matches_the_unfused_layers(cuda):
     """T = 4096 takes the gelu_bwd_t path (transposed operands written by the kernel).  Output and
     gradients against an f32 CPU evaluation, with the unfused layers (ops.linear + F.gelu) as the
     yardstick, as in the model-level test."""
+    _gelu_mlp_against_the_unfused_layers(cuda)
+
+
+def test_gelu_mlp_native_path_matches_the_unfused_layers(cuda, monkeypatch):
+    """The same with DTG_LINEAR_BWD=native: gelu_fwd + gelu_bwd and the strided GEMMs, the unfused
+    branch of the MLP backward (test_swiglu_mlp_bwd[native] is its SwiGLU twin)."""
+    from dtg.ops import functional as F_
+
+    monkeypatch.setattr(F_, "_LINEAR_BWD", "native")
+    _gelu_mlp_against_the_unfused_layers(cuda)
+
+
+def _gelu_mlp_against_the_unfused_layers(cuda):
     from dtg import ops
 
     T, Hd, I = 4096, 64, 256

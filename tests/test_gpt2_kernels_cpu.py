@@ -68,7 +68,7 @@ def test_gelu(T, I):
     C.check_gelu(CPU, T, I)
 
 
-@pytest.mark.parametrize("T,I", [(8, 8), (72, 136)])
+@pytest.mark.parametrize("T,I", [(8, 8), (72, 136), (136, 264)])
 def test_gelu_bwd_t(T, I):
     C.check_gelu_bwd_t(CPU, T, I)
 

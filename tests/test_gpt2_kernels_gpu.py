@@ -62,7 +62,7 @@ def test_gelu(cuda, T, I):
     C.check_gelu(cuda, T, I)
 
 
-@pytest.mark.parametrize("T,I", [(8, 8), (72, 136)])
+@pytest.mark.parametrize("T,I", [(8, 8), (72, 136), (136, 264)])
 def test_gelu_bwd_t(cuda, T, I):
     C.check_gelu_bwd_t(cuda, T, I)
 

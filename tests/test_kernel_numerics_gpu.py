@@ -76,14 +76,17 @@ def test_swiglu(cuda, T, I):
     C.check_swiglu(cuda, T, I)
 
 
-@pytest.mark.parametrize("T,I", [(8, 8), (72, 136)])
+@pytest.mark.parametrize("T,I", [(8, 8), (72, 136), (136, 264)])
 def test_swiglu_bwd_t(cuda, T, I):
     C.check_swiglu_bwd_t(cuda, T, I)
 
 
 def test_swiglu_refuses_bad_layouts(cuda):
     """I % 8 != 0 and a non-unit inner stride: refused by the forward and the backward alike (the
-    backward used to launch I / 8 vectors per row and leave the rest of dgu unwritten)."""
+    backward used to launch I / 8 vectors per row and leave the rest of dgu unwritten).  The tiled
+    backward refuses a gu whose width is no multiple of 16 and a dh that is not 2-D (it used to
+    take both and truncate)."""
+    C.check_swiglu_bwd_t_refusals(cuda)
     odd = torch.zeros(4, 24, dtype=BF, device=cuda)            # I = 12
     cols = torch.zeros(32, 4, dtype=BF, device=cuda).t()       # [4, 32] with stride(1) == 4
     assert cols.shape == (4, 32) and cols.stride(1) != 1

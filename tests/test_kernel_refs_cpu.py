@@ -46,9 +46,13 @@ def test_swiglu(T, I):
     C.check_swiglu(CPU, T, I)
 
 
-@pytest.mark.parametrize("T,I", [(8, 8), (72, 136)])
+@pytest.mark.parametrize("T,I", [(8, 8), (72, 136), (136, 264)])
 def test_swiglu_bwd_t(T, I):
     C.check_swiglu_bwd_t(CPU, T, I)
+
+
+def test_swiglu_bwd_t_refuses_bad_layouts():
+    C.check_swiglu_bwd_t_refusals(CPU)
 
 
 @pytest.mark.parametrize("V", C.CE_VOCABS)
