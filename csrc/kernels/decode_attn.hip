@@ -1,0 +1,413 @@
+// KV-cache generation kernels: the cache append (RoPE + scatter of k / v) and the split-KV decode
+// attention of one query token per sequence against its cache row.
+//
+// Cache layout: one K and one V tensor per layer, bf16 [rows_max, nkv, S_max, D], head-major: the
+// keys of one kv head are contiguous along the sequence, so a workgroup streams its chunk linearly.
+//
+// kv_cache_append_: per token t of the fused projection output qkv [T, (nq + 2 nkv) D], rotates the
+// q and k heads in place at pos[t] with rope.hip's pairing (i, i + D/2), operation order and single
+// rounding (the roped bits equal rope_'s), then copies the roped k and the v heads to
+// cache[rows[t], :, pos[t], :].  Empty tables = already roped (Qwen3 ropes in qk_norm_rope_fwd_):
+// copy only.  A token whose pos / rows lie outside the cache (or, when roping, whose pos lies past
+// the tables) is skipped entirely.  Thread mapping as rope.hip: one thread per (token, head, 8-pair
+// group), two 16-B accesses each way.
+//
+// decode_attn: grid (sequence, kv head, split), launched flattened.  A workgroup (4 waves) serves all
+// G = nq / nkv query heads of its kv head over its chunk of keys, so K and V are read once per
+// group.  QK and PV run on the VALU in f32 (the kernel is bound by the K / V stream; P is NOT
+// rounded to bf16).  K / V go straight to VGPRs in 16-B pieces: a key is D/8 lanes, a lane keeps
+// its 8 dims of q (pre-scaled) and of the G output accumulators, the score is a sub-wave
+// butterfly.  Each lane group carries its own online-softmax state over the keys it sees; the
+// groups of a wave are merged by shuffles, the 4 waves through LDS, in a fixed order.  With one
+// split the workgroup normalises and writes bf16 itself; otherwise it writes the f32 partial
+// (max, sum, unnormalised output) and decode_combine_kernel merges the splits in index order.
+// No atomics, no arrival counters: bitwise reproducible.  A split without keys for its row leaves
+// max = -inf, sum = 0; every exp(m - m_new) is guarded by m == -inf, so the empty partial
+// contributes 0 instead of exp(-inf + inf) = NaN.  Keys outside the attended range are never
+// loaded (the cache may hold anything there, NaN included).
+#include "common.h"
+#include "decode_attn_plan.h"
+
+#include <ATen/hip/HIPContext.h>
+
+namespace dtg {
+
+namespace {
+
+template <int W>
+__device__ __forceinline__ float lanes_sum(float v) {
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+  return v;
+}
+
+// exp(m - m_new) of a running max that may still be -inf (nothing seen): weight 0, never NaN
+__device__ __forceinline__ float rescale(float m, float m_new) { return m == -INFINITY ? 0.f : __expf(m - m_new); }
+
+template <int D, bool ROPE>
+__global__ __launch_bounds__(256) void kv_append_kernel(
+    uint16_t* __restrict__ qkv, int64_t row_stride, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc,
+    const float* __restrict__ cos_t, const float* __restrict__ sin_t, int64_t max_pos,
+    const int64_t* __restrict__ pos, const int32_t* __restrict__ rows, int nq, int nkv, int64_t T, int64_t rows_max,
+    int64_t S_max) {
+  constexpr int HALF = D / 2;
+  constexpr int GROUPS = HALF / 8;
+  const int nh = nq + 2 * nkv;
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= T * nh * GROUPS) return;
+  const int grp = gid % GROUPS;
+  const int64_t th = gid / GROUPS;
+  const int head = th % nh;
+  const int64_t tok = th / nh;
+  const int64_t p = pos[tok];
+  const int64_t r = rows[tok];
+  if (p < 0 || p >= S_max || r < 0 || r >= rows_max) return;
+  if (ROPE && p >= max_pos) return;
+  uint16_t* base = qkv + tok * row_stride + (int64_t)head * D + grp * 8;
+  u16x8 b1 = *reinterpret_cast<const u16x8*>(base);
+  u16x8 b2 = *reinterpret_cast<const u16x8*>(base + HALF);
+  if (ROPE && head < nq + nkv) {
+    float x1[8], x2[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      x1[j] = bf2f(b1[j]);
+      x2[j] = bf2f(b2[j]);
+    }
+    const float4* cp = reinterpret_cast<const float4*>(cos_t + p * HALF + grp * 8);
+    const float4* sp = reinterpret_cast<const float4*>(sin_t + p * HALF + grp * 8);
+    float4 c0 = cp[0], c1 = cp[1], s0 = sp[0], s1 = sp[1];
+    float c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+    float s[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    float o1[8], o2[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {  // rope.hip's expressions: the same bits
+      o1[j] = x1[j] * c[j] - x2[j] * s[j];
+      o2[j] = x2[j] * c[j] + x1[j] * s[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      b1[j] = f2bf(o1[j]);
+      b2[j] = f2bf(o2[j]);
+    }
+    *reinterpret_cast<u16x8*>(base) = b1;
+    *reinterpret_cast<u16x8*>(base + HALF) = b2;
+  }
+  if (head >= nq) {
+    const bool is_k = head < nq + nkv;
+    const int kvh = is_k ? head - nq : head - nq - nkv;
+    uint16_t* dst = (is_k ? kc : vc) + ((r * nkv + kvh) * S_max + p) * D + grp * 8;
+    *reinterpret_cast<u16x8*>(dst) = b1;
+    *reinterpret_cast<u16x8*>(dst + HALF) = b2;
+  }
+}
+
+template <int D, int G>
+__global__ __launch_bounds__(decode::kThreads) void decode_attn_kernel(
+    const uint16_t* __restrict__ qkv, int64_t q_stride, const uint16_t* __restrict__ kc,
+    const uint16_t* __restrict__ vc, const int32_t* __restrict__ rows, const int32_t* __restrict__ lens,
+    float* __restrict__ ws_o, float* __restrict__ ws_ml, uint16_t* __restrict__ out, int nkv, int splits,
+    int64_t chunk, int64_t window, int64_t rows_max, int64_t S_max, float scale) {
+  constexpr int LPK = D / 8;                      // lanes per key
+  constexpr int KPW = kWave / LPK;                // keys per wave per load
+  constexpr int NW = decode::kThreads / kWave;    // waves
+  constexpr int KSTEP = NW * KPW;                 // keys per workgroup per load
+  constexpr int UN = decode::kKeyTile / KSTEP;    // loads in flight per lane and tensor
+  static_assert(UN >= 1 && UN * KSTEP == decode::kKeyTile, "key tile");
+  __shared__ float sm_o[NW][G][D];
+  __shared__ float sm_m[NW][G], sm_l[NW][G];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, sub = lane / LPK, li = lane % LPK;
+  const int split = blockIdx.x % splits;
+  const int h = (blockIdx.x / splits) % nkv;
+  const int64_t b = blockIdx.x / ((int64_t)splits * nkv);
+  const int64_t row = rows[b];
+  int64_t len = lens[b];
+  if (row < 0 || row >= rows_max || len < 0) len = 0;
+  if (len > S_max) len = S_max;
+  const int64_t lo = window > 0 && len > window ? len - window : 0;
+  const int64_t k0 = lo > split * chunk ? lo : split * chunk;
+  // the last split runs to the end of the row even if max_len understated it: slow, never wrong
+  const int64_t k1 = split == splits - 1 || len < (split + 1) * chunk ? len : (split + 1) * chunk;
+
+  float q[G][8], acc[G][8], m[G], l[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    load8(qkv + b * q_stride + ((int64_t)h * G + g) * D + li * 8, q[g]);
+    m[g] = -INFINITY;
+    l[g] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      q[g][i] *= scale;
+      acc[g][i] = 0.f;
+    }
+  }
+
+  const int64_t head_off = ((k1 > k0 ? row : 0) * nkv + h) * S_max * D + li * 8;
+  const uint16_t* kb = kc + head_off;
+  const uint16_t* vb = vc + head_off;
+  for (int64_t j0 = k0; j0 < k1; j0 += decode::kKeyTile) {
+    u16x8 kr[UN], vr[UN];
+    bool ok[UN];
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int64_t j = j0 + u * KSTEP + wave * KPW + sub;
+      ok[u] = j < k1;
+      kr[u] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      vr[u] = kr[u];
+      if (ok[u]) {
+        kr[u] = *reinterpret_cast<const u16x8*>(kb + j * D);
+        vr[u] = *reinterpret_cast<const u16x8*>(vb + j * D);
+      }
+    }
+    float sc[UN][G];
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      float kf[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) kf[i] = bf2f(kr[u][i]);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        float d = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d += q[g][i] * kf[i];
+        d = lanes_sum<LPK>(d);
+        sc[u][g] = ok[u] ? d : -INFINITY;
+      }
+    }
+    float vf[UN][8];
+#pragma unroll
+    for (int u = 0; u < UN; ++u)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) vf[u][i] = bf2f(vr[u][i]);
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      float mn = m[g];
+#pragma unroll
+      for (int u = 0; u < UN; ++u) mn = fmaxf(mn, sc[u][g]);
+      const float alpha = rescale(m[g], mn);
+      float p[UN], ps = 0.f;
+#pragma unroll
+      for (int u = 0; u < UN; ++u) {
+        p[u] = rescale(sc[u][g], mn);
+        ps += p[u];
+      }
+      m[g] = mn;
+      l[g] = l[g] * alpha + ps;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        float a = acc[g][i] * alpha;
+#pragma unroll
+        for (int u = 0; u < UN; ++u) a += p[u] * vf[u][i];
+        acc[g][i] = a;
+      }
+    }
+  }
+
+  // merge the lane groups of the wave (butterfly over the group index), then the waves through LDS
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+#pragma unroll
+    for (int o = LPK; o < kWave; o <<= 1) {
+      const float mo = __shfl_xor(m[g], o, kWave), lo_ = __shfl_xor(l[g], o, kWave);
+      const float mn = fmaxf(m[g], mo);
+      const float a = rescale(m[g], mn), bw = rescale(mo, mn);
+      l[g] = l[g] * a + lo_ * bw;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[g][i] = acc[g][i] * a + __shfl_xor(acc[g][i], o, kWave) * bw;
+      m[g] = mn;
+    }
+    if (sub == 0) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) sm_o[wave][g][li * 8 + i] = acc[g][i];
+      if (li == 0) {
+        sm_m[wave][g] = m[g];
+        sm_l[wave][g] = l[g];
+      }
+    }
+  }
+  __syncthreads();
+  const int64_t bh = b * nkv + h;
+  for (int e = tid; e < G * D; e += decode::kThreads) {
+    const int g = e / D, d = e % D;
+    float mn = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) mn = fmaxf(mn, sm_m[w][g]);
+    float o = 0.f, ls = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const float wt = rescale(sm_m[w][g], mn);
+      o += sm_o[w][g][d] * wt;
+      ls += sm_l[w][g] * wt;
+    }
+    if (splits == 1) {
+      out[(bh * G + g) * D + d] = f2bf(ls > 0.f ? o / ls : 0.f);
+    } else {
+      const int64_t pi = (bh * splits + split) * G + g;
+      ws_o[pi * D + d] = o;
+      if (d == 0) {
+        ws_ml[pi * 2] = mn;
+        ws_ml[pi * 2 + 1] = ls;
+      }
+    }
+  }
+}
+
+// One workgroup per (sequence, kv head): the partials of the splits merged in index order.
+template <int D>
+__global__ __launch_bounds__(decode::kThreads) void decode_combine_kernel(
+    const float* __restrict__ ws_o, const float* __restrict__ ws_ml, uint16_t* __restrict__ out, int G, int splits) {
+  const int64_t bh = blockIdx.x;
+  for (int e = threadIdx.x; e < G * D; e += decode::kThreads) {
+    const int g = e / D, d = e % D;
+    float mn = -INFINITY;
+    for (int s = 0; s < splits; ++s) mn = fmaxf(mn, ws_ml[((bh * splits + s) * G + g) * 2]);
+    float o = 0.f, ls = 0.f;
+    for (int s = 0; s < splits; ++s) {
+      const int64_t pi = (bh * splits + s) * G + g;
+      const float ms = ws_ml[pi * 2];
+      if (ms == -INFINITY) continue;  // an empty split: nothing to add, and its output is not read
+      const float wt = __expf(ms - mn);
+      o += ws_o[pi * D + d] * wt;
+      ls += ws_ml[pi * 2 + 1] * wt;
+    }
+    out[(bh * G + g) * D + d] = f2bf(ls > 0.f ? o / ls : 0.f);
+  }
+}
+
+void check_cache(const at::Tensor& k_cache, const at::Tensor& v_cache, int64_t nkv, int64_t D, const char* name) {
+  DTG_CHECK_CUDA_BF16(k_cache);
+  DTG_CHECK_CUDA_BF16(v_cache);
+  DTG_CHECK(k_cache.dim() == 4 && k_cache.is_contiguous() && v_cache.is_contiguous() &&
+                k_cache.sizes() == v_cache.sizes() && k_cache.size(1) == nkv && k_cache.size(3) == D,
+            name, ": caches must be contiguous bf16 [rows_max, nkv, S_max, head_dim]");
+  DTG_CHECK(k_cache.numel() < (int64_t(1) << 46), name, ": cache too large");
+}
+
+void check_qkv(const at::Tensor& qkv, int64_t nq, int64_t nkv, int64_t D, const char* name) {
+  DTG_CHECK_CUDA_BF16(qkv);
+  DTG_CHECK(D == 64 || D == 128, name, ": head_dim must be 64 or 128");
+  DTG_CHECK(nq >= 1 && nkv >= 1 && nq % nkv == 0 && nq + 2 * nkv < (1 << 20), name, ": bad head counts");
+  DTG_CHECK(qkv.dim() == 2 && qkv.stride(1) == 1 && qkv.stride(0) % 8 == 0 &&
+                reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+            name, ": qkv must be [T, C] with 16-B aligned rows");
+  DTG_CHECK(qkv.size(1) >= (nq + 2 * nkv) * D, name, ": not enough columns for the q, k and v heads");
+  DTG_CHECK(qkv.size(0) == 0 || qkv.stride(0) >= qkv.size(1), name, ": overlapping rows");
+}
+
+void check_index(const at::Tensor& t, int64_t n, const char* name, const char* what) {
+  DTG_CHECK(t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous() && t.numel() == n, name, ": ", what,
+            " must be an int32 GPU tensor with one entry per token");
+}
+
+}  // namespace
+
+void kv_cache_append_(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                      const at::Tensor& cos_t, const at::Tensor& sin_t, const at::Tensor& pos, const at::Tensor& rows,
+                      int64_t nq, int64_t nkv, int64_t head_dim) {
+  const char* name = "kv_cache_append_";
+  const int64_t D = head_dim;
+  check_qkv(qkv, nq, nkv, D, name);
+  check_cache(k_cache, v_cache, nkv, D, name);
+  const int64_t T = qkv.size(0);
+  check_index(rows, T, name, "rows");
+  DTG_CHECK(pos.is_cuda() && pos.scalar_type() == at::kLong && pos.is_contiguous() && pos.numel() == T, name,
+            ": position ids must be int64 [T]");
+  const bool rope = cos_t.numel() > 0;
+  if (rope) {
+    DTG_CHECK(cos_t.is_cuda() && sin_t.is_cuda() && cos_t.scalar_type() == at::kFloat &&
+                  sin_t.scalar_type() == at::kFloat && cos_t.dim() == 2 && cos_t.is_contiguous() &&
+                  sin_t.is_contiguous() && cos_t.size(1) == D / 2 && sin_t.sizes() == cos_t.sizes(),
+              name, ": tables must be contiguous f32 [max_pos, D/2]");
+  } else {
+    DTG_CHECK(sin_t.numel() == 0, name, ": cos and sin must both be empty for the copy-only form");
+  }
+  if (T == 0) return;
+  const c10::DeviceGuard g(qkv.device());
+  const int64_t total = T * (nq + 2 * nkv) * (D / 16);
+  const int64_t nblk = (total + 255) / 256;
+  DTG_CHECK(nblk < (int64_t(1) << 31), name, ": too many tokens");
+  const float* cp = rope ? cos_t.data_ptr<float>() : nullptr;
+  const float* sp = rope ? sin_t.data_ptr<float>() : nullptr;
+  const int64_t max_pos = rope ? cos_t.size(0) : 0;
+#define DTG_APPEND_LAUNCH(D_, R_)                                                                                  \
+  kv_append_kernel<D_, R_><<<(unsigned)nblk, 256, 0, stream()>>>(                                                  \
+      bf16_mut(qkv), qkv.stride(0), bf16_mut(k_cache), bf16_mut(v_cache), cp, sp, max_pos, pos.data_ptr<int64_t>(), \
+      rows.data_ptr<int32_t>(), (int)nq, (int)nkv, T, k_cache.size(0), k_cache.size(2))
+  if (D == 128) {
+    if (rope) DTG_APPEND_LAUNCH(128, true); else DTG_APPEND_LAUNCH(128, false);
+  } else {
+    if (rope) DTG_APPEND_LAUNCH(64, true); else DTG_APPEND_LAUNCH(64, false);
+  }
+#undef DTG_APPEND_LAUNCH
+  DTG_LAUNCH_CHECK();
+}
+
+at::Tensor decode_attn(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                       const at::Tensor& rows, const at::Tensor& lens, int64_t nq, int64_t nkv, int64_t head_dim,
+                       double scale, int64_t max_len, int64_t window, int64_t splits) {
+  const char* name = "decode_attn";
+  const int64_t D = head_dim;
+  check_qkv(qkv, nq, nkv, D, name);
+  const int64_t G = nq / nkv;
+  DTG_CHECK(decode::group_ok(G), name, ": query heads per kv head must be one of 1, 2, 3, 4, 7, 8, 16");
+  check_cache(k_cache, v_cache, nkv, D, name);
+  const int64_t B = qkv.size(0), S_max = k_cache.size(2);
+  check_index(rows, B, name, "rows");
+  check_index(lens, B, name, "lens");
+  DTG_CHECK(max_len >= 0 && max_len <= S_max, name, ": max_len must lie in [0, S_max]");
+  DTG_CHECK(window >= 0 && splits >= 0, name, ": window and splits must not be negative");
+  const c10::DeviceGuard dg(qkv.device());
+  auto out = at::empty({B, nq * D}, qkv.options());
+  if (B == 0) return out;
+  const int cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  const decode::Plan p = decode::plan({B, (int)nkv, (int)G, (int)D, max_len, window, cus, (int)splits});
+  const int64_t nwg = (int64_t)p.grid.x * p.grid.y * p.grid.z;
+  DTG_CHECK(nwg < (int64_t(1) << 31), name, ": too many workgroups");
+  float *ws_o = nullptr, *ws_ml = nullptr;
+  at::Tensor ws;
+  if (p.splits > 1) {  // [B nkv splits G D] outputs, then [B nkv splits G 2] max | sum
+    ws = at::empty({(int64_t)(p.ws_bytes / sizeof(float))}, qkv.options().dtype(at::kFloat));
+    ws_o = ws.data_ptr<float>();
+    ws_ml = ws_o + B * nkv * p.splits * G * D;
+  }
+#define DTG_DECODE_LAUNCH(D_, G_)                                                                                   \
+  decode_attn_kernel<D_, G_><<<(unsigned)nwg, decode::kThreads, 0, stream()>>>(                                     \
+      bf16_ptr(qkv), qkv.stride(0), bf16_ptr(k_cache), bf16_ptr(v_cache), rows.data_ptr<int32_t>(),                 \
+      lens.data_ptr<int32_t>(), ws_o, ws_ml, bf16_mut(out), (int)nkv, p.splits, p.chunk, window, k_cache.size(0), \
+      S_max, (float)scale)
+#define DTG_DECODE_G(D_)                                  \
+  switch (G) {                                            \
+    case 1: DTG_DECODE_LAUNCH(D_, 1); break;              \
+    case 2: DTG_DECODE_LAUNCH(D_, 2); break;              \
+    case 3: DTG_DECODE_LAUNCH(D_, 3); break;              \
+    case 4: DTG_DECODE_LAUNCH(D_, 4); break;              \
+    case 7: DTG_DECODE_LAUNCH(D_, 7); break;              \
+    case 8: DTG_DECODE_LAUNCH(D_, 8); break;              \
+    default: DTG_DECODE_LAUNCH(D_, 16); break;            \
+  }
+  if (D == 128) {
+    DTG_DECODE_G(128)
+  } else {
+    DTG_DECODE_G(64)
+  }
+#undef DTG_DECODE_G
+#undef DTG_DECODE_LAUNCH
+  DTG_LAUNCH_CHECK();
+  if (p.splits > 1) {
+    if (D == 128)
+      decode_combine_kernel<128><<<(unsigned)(B * nkv), decode::kThreads, 0, stream()>>>(ws_o, ws_ml, bf16_mut(out),
+                                                                                         (int)G, p.splits);
+    else
+      decode_combine_kernel<64><<<(unsigned)(B * nkv), decode::kThreads, 0, stream()>>>(ws_o, ws_ml, bf16_mut(out),
+                                                                                        (int)G, p.splits);
+    DTG_LAUNCH_CHECK();
+  }
+  return out;
+}
+
+TORCH_LIBRARY_IMPL(dtg, CUDA, m) {
+  m.impl("kv_cache_append_", &kv_cache_append_);
+  m.impl("decode_attn", &decode_attn);
+}
+
+}  // namespace dtg

@@ -7,3 +7,11 @@ models (`dtg.models`), RCCL-based parallel engines (`dtg.parallel`) and the trai
 driver, checkpointing and observability (`dtg.train`, `dtg.utils`).
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):  # `from dtg import generate` without importing torch at `import dtg`
+    if name == "generate":
+        from .models.generation import generate
+
+        return generate
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -2,6 +2,7 @@
 import torch
 
 from .config import GPT2Config, LlamaConfig, available_configs, resolve_config
+from .generation import KVCache, decode_step, generate, prefill
 from .gpt2 import GPT2LMHeadModel
 from .llama import CausalLMOutput, LlamaForCausalLM, count_valid_labels
 
@@ -59,4 +60,4 @@ def resize_token_embeddings(model, new_vocab: int):
 
 __all__ = ["GPT2Config", "LlamaConfig", "available_configs", "resolve_config", "GPT2LMHeadModel",
            "LlamaForCausalLM", "CausalLMOutput", "count_valid_labels", "build_model", "resize_token_embeddings",
-           "mean_resized_rows"]
+           "mean_resized_rows", "KVCache", "prefill", "decode_step", "generate"]

@@ -1,0 +1,220 @@
+"""KV-cache generation for the Llama-family models (llama, mistral, qwen2, qwen3).
+
+`prefill` runs the packed prompts through the layers exactly as the packed training path does
+(token-major, cu_seqlens / position ids restarting per prompt, varlen flash attention) while
+`ops.kv_cache_append` ropes q / k and fills the cache; `decode_step` runs one token per sequence
+through `ops.kv_cache_append` and the split-KV `ops.decode_attention`.  The norms, projections and
+MLP are the training ops, unchanged.  Logits are computed for the last token of each sequence only:
+no [T, V] tensor exists.
+
+Not covered (ValueError): GPT-2, and models built with a tensor-, context- or Ulysses-parallel group.
+Mistral's sliding window is passed to both attention paths; the cache keeps the full length (no
+ring buffer).
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence
+
+import torch
+
+from .. import ops
+from .gpt2 import GPT2LMHeadModel
+from .llama import LlamaForCausalLM
+
+HOST_CHECK_EVERY = 16  # steps between host reads of the device-side done mask
+
+
+def _check_model(model):
+    if isinstance(model, GPT2LMHeadModel):
+        raise ValueError("generate: GPT-2 is not supported yet (Llama-family models only)")
+    if not isinstance(model, LlamaForCausalLM):
+        raise ValueError(f"generate: unsupported model type {type(model).__name__}")
+    if model.tp.group is not None or model.cp_group is not None or model.sp_group is not None:
+        raise ValueError("generate: models built with a tensor-, context- or Ulysses-parallel group are not supported yet")
+
+
+class KVCache:
+    """Per-layer K / V tensors [rows_max, nkv, S_max, D] (head-major: one kv head's keys are contiguous
+    along the sequence), the device-side length of every row, and a host upper bound of those lengths
+    for the decode kernel's launch plan."""
+
+    def __init__(self, cfg, rows_max: int, s_max: int, device=None, dtype=torch.bfloat16):
+        if rows_max < 1 or s_max < 1:
+            raise ValueError(f"KVCache: rows_max ({rows_max}) and S_max ({s_max}) must be positive")
+        self.rows_max, self.s_max = int(rows_max), int(s_max)
+        shape = (self.rows_max, cfg.num_key_value_heads, self.s_max, cfg.head_dim)
+        self.k = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(cfg.num_hidden_layers)]
+        self.v = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(cfg.num_hidden_layers)]
+        self.lens = torch.zeros(self.rows_max, dtype=torch.int32, device=device)
+        self.max_len = 0  # host: no row is longer than this
+
+    def reset(self):
+        self.lens.zero_()
+        self.max_len = 0
+
+
+def _run_layers(model, x, append_and_attend):
+    """The decoder stack around a caller-supplied attention (qkv -> attention output)."""
+    res = None
+    for i, layer in enumerate(model.layers):
+        if res is None:
+            n, res = ops.rms_norm(x, layer.input_layernorm.weight, layer.eps), x
+        else:
+            n, res = ops.add_rms_norm(x, res, layer.input_layernorm.weight, layer.eps)
+        attn = layer.self_attn
+        b = getattr(attn.qkv_proj, "bias", None)
+        qkv = ops.linear(n, attn.qkv_proj.weight, None if b is None else b.view(-1))
+        a = ops.linear(append_and_attend(i, attn, qkv), attn.o_proj.weight)
+        n2, res = ops.add_rms_norm(a, res, layer.post_attention_layernorm.weight, layer.eps)
+        x = layer.mlp(n2)
+    return x, res
+
+
+def _append(attn, qkv, cache, i, cos, sin, pos, rows, pos_max):
+    """RoPE (after the per-head norm for Qwen3, whose fused pass ropes itself) and the cache write.
+    `pos_max`: the host's largest position of the call, checked by the op (rows were checked by _rows)."""
+    if attn.qk_norm:
+        qkv = ops.qk_norm_rope(qkv, attn.q_norm.weight, attn.k_norm.weight, attn.eps, attn.nq, attn.nkv, attn.d,
+                               cos, sin, pos)
+        return ops.kv_cache_append(qkv, cache.k[i], cache.v[i], pos, rows, attn.nq, attn.nkv, attn.d, pos_max=pos_max)
+    return ops.kv_cache_append(qkv, cache.k[i], cache.v[i], pos, rows, attn.nq, attn.nkv, attn.d, cos, sin,
+                               pos_max=pos_max)
+
+
+def _last_logits(model, x, res):
+    h, _ = ops.add_rms_norm(x, res, model.norm.weight, model.config.rms_norm_eps)
+    return ops.linear(h, model.lm_head_weight())
+
+
+def _rows(cache, n, rows, device):
+    if rows is None:
+        rows_host = list(range(n))
+    else:
+        rows_host = [int(r) for r in rows]
+    if len(rows_host) != n or len(set(rows_host)) != n or any(not 0 <= r < cache.rows_max for r in rows_host):
+        raise ValueError(f"cache rows {rows_host} must be {n} distinct rows in [0, {cache.rows_max})")
+    return torch.tensor(rows_host, dtype=torch.int32, device=device)
+
+
+@torch.no_grad()
+def prefill(model, prompts: Sequence[torch.Tensor], cache: KVCache, rows: Optional[Sequence[int]] = None):
+    """Run the prompts (1-D id tensors of any lengths >= 1) packed token-major, fill cache rows `rows`
+    (default 0..n-1) from position 0 and return the logits [n, V] of each prompt's last token."""
+    _check_model(model)
+    lens = [int(p.numel()) for p in prompts]
+    if not lens or min(lens) < 1:
+        raise ValueError("prefill: every prompt needs at least one token")
+    if max(lens) > cache.s_max:
+        raise ValueError(f"prefill: a prompt of {max(lens)} tokens does not fit the cache (S_max = {cache.s_max})")
+    dev = cache.lens.device
+    rows_t = _rows(cache, len(lens), rows, dev)
+    ids = torch.cat([p.reshape(-1) for p in prompts]).to(dev)
+    lens_t = torch.tensor(lens, dtype=torch.int32, device=dev)
+    pos = torch.cat([torch.arange(n, dtype=torch.long) for n in lens]).to(dev)
+    cu = torch.tensor([0] + lens, dtype=torch.int32).cumsum(0).to(torch.int32).to(dev)
+    tok_rows = torch.repeat_interleave(rows_t, lens_t.long(), output_size=sum(lens))
+    cos, sin = model._rope_tables(cache.s_max, dev)
+    max_seqlen = max(lens)
+
+    def attend(i, attn, qkv):
+        qkv = _append(attn, qkv, cache, i, cos, sin, pos, tok_rows, max_seqlen - 1)
+        return ops.attention(qkv, attn.nq, attn.nkv, attn.d, cu, max_seqlen, window=attn.window)  # q, k roped already
+
+    x, res = _run_layers(model, ops.embedding(ids, model.embed_tokens.weight), attend)
+    last = (cu[1:] - 1).long()
+    cache.lens[rows_t.long()] = lens_t
+    cache.max_len = max(cache.max_len, max_seqlen)
+    return _last_logits(model, x[last], res[last])
+
+
+@torch.no_grad()
+def decode_step(model, tokens: torch.Tensor, cache: KVCache, rows: Optional[Sequence[int]] = None):
+    """One new token per active sequence (`tokens` [n], for cache rows `rows`, default 0..n-1): appends
+    it at the row's current length and returns the next-token logits [n, V]."""
+    _check_model(model)
+    if cache.max_len + 1 > cache.s_max:
+        raise ValueError(f"decode_step: the cache is full (S_max = {cache.s_max})")
+    dev = cache.lens.device
+    tokens = tokens.reshape(-1).to(dev)
+    rows_t = _rows(cache, tokens.numel(), rows, dev)
+    pos = cache.lens[rows_t.long()].long()
+    new_lens = (pos + 1).to(torch.int32)
+    cos, sin = model._rope_tables(cache.s_max, dev)
+    max_len = cache.max_len + 1
+
+    def attend(i, attn, qkv):
+        qkv = _append(attn, qkv, cache, i, cos, sin, pos, rows_t, max_len - 1)
+        return ops.decode_attention(qkv, cache.k[i], cache.v[i], rows_t, new_lens, attn.nq, attn.nkv, attn.d, max_len,
+                                    window=attn.window)
+
+    x, res = _run_layers(model, ops.embedding(tokens, model.embed_tokens.weight), attend)
+    cache.lens[rows_t.long()] = new_lens
+    cache.max_len = max_len
+    return _last_logits(model, x, res)
+
+
+def sample_next(logits, temperature=0.0, top_k=0, top_p=1.0, generator=None):
+    """Next ids [n] from logits [n, V]: argmax at temperature 0, else a draw from the softmax of
+    logits / temperature restricted to the top_k ids and the smallest set whose mass reaches top_p."""
+    if temperature <= 0.0:
+        return logits.argmax(-1)
+    z = logits.float() / float(temperature)
+    if top_k and top_k < z.shape[-1]:
+        kth = z.topk(int(top_k), -1).values[:, -1:]
+        z = z.masked_fill(z < kth, float("-inf"))
+    if top_p < 1.0:
+        sz, si = z.sort(-1, descending=True)
+        p = torch.softmax(sz, -1)
+        drop = (p.cumsum(-1) - p) >= float(top_p)  # mass before this id already reaches top_p; the top id stays
+        z = z.masked_fill(torch.zeros_like(drop).scatter(-1, si, drop), float("-inf"))
+    return torch.multinomial(torch.softmax(z, -1), 1, generator=generator).squeeze(-1)
+
+
+@torch.no_grad()
+def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
+             top_p: float = 1.0, eos_token_id: Optional[int] = None, seed: int = 0, s_max: Optional[int] = None
+             ) -> List[torch.Tensor]:
+    """Continue every prompt by up to `max_new_tokens` ids; returns the new ids of each sequence (1-D
+    int64 tensors on the CPU), ending with `eos_token_id` where the sequence produced it.
+
+    Greedy at temperature 0, else sampled with a torch.Generator seeded with `seed`.  The per-sequence
+    done mask lives on the device and is read on the host every HOST_CHECK_EVERY steps only; finished
+    sequences keep running (their ids are discarded) until all are done or the budget is spent.
+    `s_max` sizes the cache (default: longest prompt + max_new_tokens); prompt + max_new_tokens beyond
+    it is an error."""
+    _check_model(model)
+    prompts = [p.reshape(-1) for p in prompts]
+    if not prompts or min(p.numel() for p in prompts) < 1:
+        raise ValueError("generate: every prompt needs at least one token")
+    if max_new_tokens < 0 or temperature < 0.0 or not 0.0 < top_p <= 1.0 or top_k < 0:
+        raise ValueError("generate: need max_new_tokens >= 0, temperature >= 0, 0 < top_p <= 1, top_k >= 0")
+    longest = max(p.numel() for p in prompts)
+    if s_max is None:
+        s_max = longest + max_new_tokens
+    if longest + max_new_tokens > s_max:
+        raise ValueError(f"generate: prompt ({longest}) + max_new_tokens ({max_new_tokens}) exceeds S_max ({s_max})")
+    n = len(prompts)
+    if max_new_tokens == 0:
+        return [torch.empty(0, dtype=torch.long) for _ in range(n)]
+    dev = model.embed_tokens.weight.device
+    gen = None
+    if temperature > 0.0:
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+    cache = KVCache(model.config, n, s_max, device=dev, dtype=model.embed_tokens.weight.dtype)
+    out = torch.zeros(n, max_new_tokens, dtype=torch.long, device=dev)
+    count = torch.zeros(n, dtype=torch.long, device=dev)  # ids kept per sequence
+    done = torch.zeros(n, dtype=torch.bool, device=dev)
+    logits = prefill(model, prompts, cache)
+    for step in range(max_new_tokens):
+        nxt = sample_next(logits, temperature, top_k, top_p, gen)
+        out[:, step] = nxt
+        count += (~done).long()
+        if eos_token_id is not None:
+            done |= nxt == int(eos_token_id)
+            if (step + 1) % HOST_CHECK_EVERY == 0 and bool(done.all()):
+                break
+        if step + 1 < max_new_tokens:
+            logits = decode_step(model, nxt, cache)
+    out, count = out.cpu(), count.tolist()
+    return [out[i, : count[i]].clone() for i in range(n)]

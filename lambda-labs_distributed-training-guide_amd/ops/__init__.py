@@ -18,10 +18,12 @@ if not _native.LOADED:  # CPU-only box without a build: host AdamW falls back to
 from .functional import (  # noqa: E402
     add_rms_norm,
     attention,
+    decode_attention,
     dropout_add_layer_norm,
     embedding,
     fused_linear_cross_entropy,
     gelu_mlp,
+    kv_cache_append,
     layer_norm,
     linear,
     qk_norm_rope,
@@ -55,5 +57,5 @@ def fa_tuning(device="cuda", kv_split: int = -1, kv_qb: int = -1):
 __all__ = [
     "add_rms_norm", "attention", "rope", "embedding", "fused_linear_cross_entropy", "linear", "rms_norm",
     "rope_tables", "swiglu", "swiglu_mlp", "vocab_parallel_fused_linear_cross_entropy", "route_param_grad", "adamw_step",
-    "fa_tuning", "layer_norm", "dropout_add_layer_norm", "gelu_mlp", "qk_norm_rope",
+    "fa_tuning", "layer_norm", "dropout_add_layer_norm", "gelu_mlp", "qk_norm_rope", "kv_cache_append", "decode_attention",
 ]

@@ -96,6 +96,54 @@ def qk_norm_rope_bwd_(dqkv, xqk, rstd, wq, wk, cos, sin, pos, nq, nkv, head_dim)
     return dw[:, :nq].sum((0, 1)).to(wq.dtype), dw[:, nq:].sum((0, 1)).to(wk.dtype)
 
 
+def kv_cache_append_(qkv, k_cache, v_cache, cos, sin, pos, rows, nq, nkv, head_dim):
+    """rope_ on the q and k heads at pos (empty tables: already roped), then k and v of every token to
+    cache[rows[t], :, pos[t], :]; tokens whose pos / rows lie outside the cache (or, when roping, past
+    the tables) are left untouched and write nothing (csrc/kernels/decode_attn.hip)."""
+    T, d = qkv.shape[0], head_dim
+    if not (k_cache.dim() == 4 and k_cache.shape == v_cache.shape and k_cache.shape[1] == nkv and k_cache.shape[3] == d):
+        raise RuntimeError("dtg: kv_cache_append_: caches must be contiguous bf16 [rows_max, nkv, S_max, head_dim]")
+    if not (qkv.dim() == 2 and qkv.shape[1] >= (nq + 2 * nkv) * d and pos.numel() == T and rows.numel() == T):
+        raise RuntimeError("dtg: kv_cache_append_: qkv must be [T, (nq + 2 nkv) * head_dim] with one pos and row per token")
+    pos, rows = pos.long(), rows.long()
+    ok = (pos >= 0) & (pos < k_cache.shape[2]) & (rows >= 0) & (rows < k_cache.shape[0])
+    if cos.numel():
+        ok &= pos < cos.shape[0]
+        sel = qkv[ok]
+        rope_(sel, cos, sin, pos[ok], nq + nkv, d, False)
+        qkv[ok] = sel
+    k = qkv[:, nq * d:(nq + nkv) * d].reshape(T, nkv, d)
+    v = qkv[:, (nq + nkv) * d:(nq + 2 * nkv) * d].reshape(T, nkv, d)
+    k_cache[rows[ok], :, pos[ok]] = k[ok]
+    v_cache[rows[ok], :, pos[ok]] = v[ok]
+
+
+def decode_attn(qkv, k_cache, v_cache, rows, lens, nq, nkv, head_dim, scale, max_len, window=0, splits=0):
+    """One query token per sequence against keys [max(0, len - window), len) of its cache row, f32
+    softmax, one rounding.  The CPU reference takes any head dim and group size; `splits` has no
+    meaning here (one pass)."""
+    B, d, g = qkv.shape[0], head_dim, nq // nkv
+    if nq % nkv or not (k_cache.dim() == 4 and k_cache.shape == v_cache.shape and k_cache.shape[1] == nkv
+                        and k_cache.shape[3] == d):
+        raise RuntimeError("dtg: decode_attn: caches must be contiguous bf16 [rows_max, nkv, S_max, head_dim]")
+    if not 0 <= max_len <= k_cache.shape[2]:
+        raise RuntimeError("dtg: decode_attn: max_len must lie in [0, S_max]")
+    out = torch.zeros(B, nq * d, dtype=qkv.dtype)
+    for b in range(B):
+        n, r = int(lens[b]), int(rows[b])
+        if not 0 <= r < k_cache.shape[0]:
+            continue
+        n = min(n, k_cache.shape[2])
+        lo = max(0, n - window) if window > 0 else 0
+        if n <= lo:
+            continue
+        q = qkv[b, : nq * d].float().reshape(nkv, g, d)
+        k, v = k_cache[r, :, lo:n].float(), v_cache[r, :, lo:n].float()
+        p = torch.softmax(torch.einsum("hgd,hsd->hgs", q, k) * scale, -1)
+        out[b] = torch.einsum("hgs,hsd->hgd", p, v).reshape(nq * d).to(qkv.dtype)
+    return out
+
+
 def swiglu_fwd(gu):
     inter = gu.shape[1] // 2
     g, u = gu[:, :inter].float(), gu[:, inter:].float()
@@ -638,6 +686,6 @@ for _name, _fn in list(globals().items()):
         "flash_attn_bwd_qkv", "transpose2d", "transpose_mats_", "swiglu_bwd_t", "embedding_bwd_", "flash_attn_varlen_fwd",
         "flash_attn_varlen_bwd", "flash_attn_fwd_drop", "flash_attn_bwd_drop", "flash_attn_bwd_qkv_drop", "philox_rng",
         "flash_attn_bwd_qkv_rope", "flash_attn_tuning", "layernorm_fwd", "dropout_add_layernorm_fwd", "layernorm_bwd",
-        "gelu_fwd", "gelu_bwd", "gelu_bwd_t", "qk_norm_rope_fwd_", "qk_norm_rope_bwd_",
+        "gelu_fwd", "gelu_bwd", "gelu_bwd_t", "qk_norm_rope_fwd_", "qk_norm_rope_bwd_", "kv_cache_append_", "decode_attn",
     ):
         LIB.impl(_name, _fn, "CPU")

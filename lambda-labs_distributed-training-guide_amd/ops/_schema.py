@@ -33,6 +33,17 @@ _DEFS = [
     "int head_dim, float eps) -> (Tensor, Tensor)",
     "qk_norm_rope_bwd_(Tensor(a!) dqkv, Tensor xqk, Tensor rstd, Tensor wq, Tensor wk, Tensor cos, Tensor sin, "
     "Tensor pos, int nq, int nkv, int head_dim) -> (Tensor, Tensor)",
+    # KV-cache generation (csrc/kernels/decode_attn.hip); caches are bf16 [rows_max, nkv, S_max, D].
+    # append: RoPE at pos[t] on the q and k heads of qkv in place (empty cos / sin = already roped, copy
+    # only), then the roped k and the v go to cache[rows[t], :, pos[t], :]; pos int64 [T], rows int32 [T];
+    # a token whose pos / rows lie outside the cache is skipped
+    "kv_cache_append_(Tensor(a!) qkv, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor cos, Tensor sin, Tensor pos, "
+    "Tensor rows, int nq, int nkv, int head_dim) -> ()",
+    # one query token per sequence (its q heads read out of the fused qkv row b) against keys
+    # [max(0, lens[b] - window), lens[b]) of cache row rows[b]; rows / lens int32 [B] on the device,
+    # max_len a host upper bound of lens (launch plan only), splits = 0 takes the plan's split count
+    "decode_attn(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor rows, Tensor lens, int nq, int nkv, int head_dim, "
+    "float scale, int max_len, int window=0, int splits=0) -> Tensor",
     "swiglu_fwd(Tensor gu) -> Tensor",
     "swiglu_bwd(Tensor dh, Tensor gu) -> Tensor",
     "swiglu_bwd_t(Tensor dh, Tensor gu) -> (Tensor, Tensor, Tensor)",

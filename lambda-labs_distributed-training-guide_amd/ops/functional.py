@@ -492,6 +492,120 @@ def attention(qkv, nq, nkv, head_dim, cu_seqlens, max_seqlen, cos=None, sin=None
 
 
 # --------------------------------------------------------------------------------------------
+# KV-cache generation: cache append and split-KV decode attention (csrc/kernels/decode_attn.hip)
+# --------------------------------------------------------------------------------------------
+# Inference only (no autograd).  DTG_DECODE_FUSED=0 composes both ops from torch ops instead (the
+# kernels' A/B partner and the yardstick of their accuracy tests); so do, on a GPU, dtypes other than
+# bf16 and head dims and group sizes the kernels are not instantiated for.
+_DECODE_FUSED = os.environ.get("DTG_DECODE_FUSED", "1") == "1"
+DECODE_GROUPS = (1, 2, 3, 4, 7, 8, 16)  # query heads per kv head the decode kernel is instantiated for
+
+
+def _decode_kernels(qkv, nq, nkv, d):
+    if not _DECODE_FUSED:
+        return False
+    return not qkv.is_cuda or (qkv.dtype == torch.bfloat16 and d in FA_HEAD_DIMS and nq // nkv in DECODE_GROUPS)
+
+
+def _check_cache_args(name, qkv, k_cache, v_cache, nq, nkv, d, index):
+    if nq < 1 or nkv < 1 or nq % nkv:
+        raise ValueError(f"{name}: nq ({nq}) must be a positive multiple of nkv ({nkv})")
+    if qkv.dim() != 2 or qkv.shape[1] != (nq + 2 * nkv) * d:
+        raise ValueError(f"{name}: qkv must be [T, (nq + 2 nkv) * head_dim], got {tuple(qkv.shape)}")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[1] != nkv or k_cache.shape[3] != d:
+        raise ValueError(f"{name}: caches must be [rows_max, {nkv}, S_max, {d}], got {tuple(k_cache.shape)} / "
+                         f"{tuple(v_cache.shape)}")
+    if k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype or not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError(f"{name}: caches must be contiguous and of qkv's dtype")
+    for what, t in index.items():
+        if t.dim() != 1 or t.numel() != qkv.shape[0] or t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{name}: {what} must be an integer tensor [{qkv.shape[0]}], got {t.dtype} {tuple(t.shape)}")
+
+
+@torch.no_grad()
+def kv_cache_append(qkv, k_cache, v_cache, pos, rows, nq, nkv, head_dim, cos=None, sin=None, pos_max=None,
+                    row_max=None):
+    """Rotate the q and k heads of the fused `qkv` [T, (nq + 2 nkv) * d] in place at `pos` (cos / sin
+    given; None = already roped, as after `qk_norm_rope`) and write every token's k and v to
+    cache[rows[t], :, pos[t], :].  Serves the packed prefill and a decode step alike.  Returns qkv.
+    `pos` / `rows` are device tensors and are not read on the host.  A caller that knows them on the
+    host passes `pos_max` / `row_max`, the largest position / row of the call: they are checked here
+    against S_max, the tables and rows_max (models/generation.py does).  Without them a token outside
+    the cache silently writes nothing."""
+    nq, nkv, d = int(nq), int(nkv), int(head_dim)
+    _check_cache_args("kv_cache_append", qkv, k_cache, v_cache, nq, nkv, d, {"pos": pos, "rows": rows})
+    if (cos is None) != (sin is None):
+        raise ValueError("kv_cache_append: pass both cos and sin, or neither")
+    if cos is not None and (cos.dim() != 2 or cos.shape[1] != d // 2 or cos.shape != sin.shape):
+        raise ValueError(f"kv_cache_append: tables must be [max_pos, {d // 2}]")
+    if pos_max is not None and not 0 <= int(pos_max) < min(k_cache.shape[2], cos.shape[0] if cos is not None else 1 << 62):
+        raise ValueError(f"kv_cache_append: position {int(pos_max)} outside the cache (S_max = {k_cache.shape[2]}) or the "
+                         f"RoPE tables")
+    if row_max is not None and not 0 <= int(row_max) < k_cache.shape[0]:
+        raise ValueError(f"kv_cache_append: cache row {int(row_max)} outside [0, {k_cache.shape[0]})")
+    pos, rows = pos.long(), rows.to(torch.int32)
+    if _decode_kernels(qkv, nq, nq, d):  # the append has no group-size limit
+        e = torch.empty(0, device=qkv.device)
+        ops.kv_cache_append_(qkv, k_cache, v_cache, e if cos is None else cos, e if sin is None else sin,
+                             pos.contiguous(), rows.contiguous(), nq, nkv, d)
+        return qkv
+    T, h = qkv.shape[0], d // 2
+    ok = (pos >= 0) & (pos < k_cache.shape[2]) & (rows >= 0) & (rows < k_cache.shape[0])
+    if cos is not None:
+        ok &= pos < cos.shape[0]
+        p = pos.clamp(0, cos.shape[0] - 1)
+        x = qkv[:, : (nq + nkv) * d].reshape(T, nq + nkv, d).float()
+        c, s = cos[p][:, None, :], sin[p][:, None, :]
+        x1, x2 = x[..., :h], x[..., h:]
+        rot = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1).reshape(T, (nq + nkv) * d).to(qkv.dtype)
+        qkv[:, : (nq + nkv) * d] = torch.where(ok[:, None], rot, qkv[:, : (nq + nkv) * d])
+    # boolean selection of the in-range tokens: one host sync, which this fallback path accepts
+    r, p = rows.long()[ok], pos[ok]
+    k_cache[r, :, p] = qkv[:, nq * d:(nq + nkv) * d].reshape(T, nkv, d)[ok]
+    v_cache[r, :, p] = qkv[:, (nq + nkv) * d:].reshape(T, nkv, d)[ok]
+    return qkv
+
+
+@torch.no_grad()
+def decode_attention(qkv, k_cache, v_cache, rows, lens, nq, nkv, head_dim, max_len, scale=None, window=0, splits=0):
+    """Attention of one query token per sequence against its KV-cache row -> [B, nq * d].
+
+    Row b's query heads are read out of the fused `qkv` row b and attend to keys
+    [max(0, lens[b] - window), lens[b]) of cache row rows[b] (window 0 = all).  `lens` / `rows` stay on
+    the device; `max_len` is a host upper bound of lens, used for the launch plan only.  `splits` > 0
+    overrides the planned split-KV count."""
+    nq, nkv, d = int(nq), int(nkv), int(head_dim)
+    _check_cache_args("decode_attention", qkv, k_cache, v_cache, nq, nkv, d, {"rows": rows, "lens": lens})
+    max_len, window, splits = int(max_len), int(window or 0), int(splits)
+    if not 0 <= max_len <= k_cache.shape[2]:
+        raise ValueError(f"decode_attention: max_len {max_len} outside [0, S_max = {k_cache.shape[2]}]")
+    if window < 0 or splits < 0:
+        raise ValueError("decode_attention: window and splits must not be negative")
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    if _decode_kernels(qkv, nq, nkv, d):
+        return ops.decode_attn(qkv, k_cache, v_cache, rows.to(torch.int32).contiguous(), lens.to(torch.int32).contiguous(),
+                               nq, nkv, d, float(scale), max_len, window, splits)
+    B, g = qkv.shape[0], nq // nkv
+    n = lens.long().clamp(0, max_len)
+    r = rows.long()
+    n = torch.where((r >= 0) & (r < k_cache.shape[0]), n, torch.zeros_like(n))
+    r = r.clamp(0, k_cache.shape[0] - 1)
+    j = torch.arange(max_len, device=qkv.device)
+    keep = j[None] < n[:, None]
+    if window > 0:
+        keep &= j[None] >= (n - window)[:, None]
+    q = qkv[:, : nq * d].reshape(B, nkv, g, d).float()
+    # masked slots may hold anything (NaN included): zero them rather than multiply them by 0
+    k = torch.where(keep[:, None, :, None], k_cache[r, :, :max_len].float(), torch.zeros((), device=qkv.device))
+    v = torch.where(keep[:, None, :, None], v_cache[r, :, :max_len].float(), torch.zeros((), device=qkv.device))
+    s = torch.einsum("bhgd,bhsd->bhgs", q, k) * float(scale)
+    s = s.masked_fill(~keep[:, None, None, :], float("-inf"))
+    p = torch.softmax(s, -1).masked_fill(~keep[:, None, None, :], 0.0)  # a row without keys: 0, not NaN
+    return torch.einsum("bhgs,bhsd->bhgd", p, v).reshape(B, nq * d).to(qkv.dtype)
+
+
+# --------------------------------------------------------------------------------------------
 # SwiGLU
 # --------------------------------------------------------------------------------------------
 class _SwiGLU(torch.autograd.Function):

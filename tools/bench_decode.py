@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""The split-KV decode attention kernel (csrc/kernels/decode_attn.hip) against the composed torch path
+(DTG_DECODE_FUSED=0) in the same process: time per call from HIP events and the rate at which the K
+and V bytes the call must read are consumed, at the Llama-3-8B head shape (nq 32, nkv 8, D 128), batch
+1 / 8 / 64 and cache lengths 1k / 8k / 32k.
+
+Bytes counted: 2 (K, V) x B x nkv x len x D bf16 values -- every sequence is `len` long, so this is what
+any implementation has to read; q, the output and the split partials are below 1 % of it.  Every shape
+is warmed up, the two paths alternate, and each timing covers at least `--min-ms` of device time.
+Needs a GPU: there is no CPU fallback for a timing.
+
+    python tools/bench_decode.py [--md OUT.md]
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+NQ, NKV, D = 32, 8, 128
+BATCHES = (1, 8, 64)
+LENGTHS = (1024, 8192, 32768)
+
+
+def time_ms(torch, fn, min_ms, rounds=3):
+    """Median over `rounds` of the mean device time per call, each round >= min_ms of work."""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    fn()
+    e.record()
+    torch.cuda.synchronize()
+    iters = max(3, min(2000, int(min_ms / max(s.elapsed_time(e), 1e-3)) + 1))
+    ts = []
+    for _ in range(rounds):
+        s.record()
+        for _ in range(iters):
+            fn()
+        e.record()
+        torch.cuda.synchronize()
+        ts.append(s.elapsed_time(e) / iters)
+    return sorted(ts)[len(ts) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--min-ms", type=float, default=200.0)
+    ap.add_argument("--md", default=None, help="also write the table as markdown here")
+    a = ap.parse_args()
+    import torch
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_decode: needs a GPU (a CPU timing says nothing about the kernel)")
+    import dtg  # noqa: F401
+    from dtg import ops
+    from dtg.ops import functional
+
+    dev = torch.device("cuda:0")
+    rows_out = []
+    for B in BATCHES:
+        for L in LENGTHS:
+            g = torch.Generator(device=dev).manual_seed(B * 100003 + L)
+            qkv = torch.randn(B, (NQ + 2 * NKV) * D, device=dev, generator=g).to(torch.bfloat16)
+            kc = torch.randn(B, NKV, L, D, device=dev, generator=g).to(torch.bfloat16)
+            vc = torch.randn(B, NKV, L, D, device=dev, generator=g).to(torch.bfloat16)
+            rows = torch.arange(B, dtype=torch.int32, device=dev)
+            lens = torch.full((B,), L, dtype=torch.int32, device=dev)
+
+            def call():
+                return ops.decode_attention(qkv, kc, vc, rows, lens, NQ, NKV, D, L)
+
+            res, outs = {}, {}
+            for fused in (True, False, True, False):  # alternate; keep the better median of each path
+                functional._DECODE_FUSED = fused
+                outs[fused] = call()
+                t = time_ms(torch, call, a.min_ms)
+                res[fused] = min(res.get(fused, t), t)
+            functional._DECODE_FUSED = True
+            diff = (outs[True].float() - outs[False].float()).abs().max().item()
+            nbytes = 2 * B * NKV * L * D * 2
+            r = {"batch": B, "len": L, "kernel_us": round(res[True] * 1e3, 1), "composed_us": round(res[False] * 1e3, 1),
+                 "kernel_GBps": round(nbytes / res[True] / 1e6, 1), "composed_GBps": round(nbytes / res[False] / 1e6, 1),
+                 "speedup": round(res[False] / res[True], 2), "max_abs_diff": round(diff, 5)}
+            print(json.dumps(r), flush=True)
+            rows_out.append(r)
+            del kc, vc
+    if a.md:
+        with open(a.md, "w") as fp:
+            fp.write("| batch | cache len | kernel µs | composed µs | kernel GB/s (K+V) | composed GB/s | composed / kernel | max abs diff |\n")
+            fp.write("|---|---|---|---|---|---|---|---|\n")
+            for r in rows_out:
+                fp.write(f"| {r['batch']} | {r['len']} | {r['kernel_us']} | {r['composed_us']} | {r['kernel_GBps']} | "
+                         f"{r['composed_GBps']} | {r['speedup']} | {r['max_abs_diff']} |\n")
+
+
+if __name__ == "__main__":
+    main()
