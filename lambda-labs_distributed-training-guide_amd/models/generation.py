@@ -7,6 +7,11 @@ through `ops.kv_cache_append` and the split-KV `ops.decode_attention`.  The norm
 MLP are the training ops, unchanged.  Logits are computed for the last token of each sequence only:
 no [T, V] tensor exists.
 
+Sampling: `generate(..., sampler="torch")` (default) keeps `sample_next`, a chain of torch ops drawn
+from one generator shared by the batch; `sampler="fused"` ends every step in the single-launch
+`ops.sample_logits` (top-k, top-p, min-p, per-prompt parameters, a counter-based draw per sequence; see
+related-topics/sampling/README.md).  The two draw different ids for one seed.
+
 Not covered (ValueError): GPT-2, and models built with a tensor-, context- or Ulysses-parallel group.
 Mistral's sliding window is passed to both attention paths; the cache keeps the full length (no
 ring buffer).
@@ -170,14 +175,32 @@ def sample_next(logits, temperature=0.0, top_k=0, top_p=1.0, generator=None):
     return torch.multinomial(torch.softmax(z, -1), 1, generator=generator).squeeze(-1)
 
 
+def _fused_params(n, **given):
+    """Per-prompt host lists of the fused sampler's parameters; every value passes the scalar rules."""
+    out = {}
+    for name, v in given.items():
+        vals = v.tolist() if isinstance(v, torch.Tensor) else (list(v) if isinstance(v, (list, tuple)) else [v] * n)
+        if len(vals) != n:
+            raise ValueError(f"generate: {name} has {len(vals)} values for {n} prompts")
+        for x in vals:
+            ops.check_sample_scalar(name, x)
+        out[name] = vals
+    return out
+
+
 @torch.no_grad()
 def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
-             top_p: float = 1.0, eos_token_id: Optional[int] = None, seed: int = 0, s_max: Optional[int] = None
-             ) -> List[torch.Tensor]:
+             top_p: float = 1.0, eos_token_id: Optional[int] = None, seed: int = 0, s_max: Optional[int] = None,
+             min_p: float = 0.0, sampler: str = "torch") -> List[torch.Tensor]:
     """Continue every prompt by up to `max_new_tokens` ids; returns the new ids of each sequence (1-D
     int64 tensors on the CPU), ending with `eos_token_id` where the sequence produced it.
 
-    Greedy at temperature 0, else sampled with a torch.Generator seeded with `seed`.  The per-sequence
+    sampler="torch" (default): greedy at temperature 0, else `sample_next` with one torch.Generator
+    seeded with `seed` for the whole batch.  sampler="fused": every step is one `ops.sample_logits`
+    call (seed = `seed`, stream = the prompt's index, step = a device counter), so what a sequence
+    draws does not depend on the other prompts of the batch; `temperature`, `top_k`, `top_p` and `min_p`
+    may then each be a sequence with one value per prompt (a temperature of 0 makes that prompt greedy
+    while the others sample).  The two samplers draw different ids for the same seed.  The per-sequence
     done mask lives on the device and is read on the host every HOST_CHECK_EVERY steps only; finished
     sequences keep running (their ids are discarded) until all are done or the budget is spent.
     `s_max` sizes the cache (default: longest prompt + max_new_tokens); prompt + max_new_tokens beyond
@@ -186,8 +209,22 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     prompts = [p.reshape(-1) for p in prompts]
     if not prompts or min(p.numel() for p in prompts) < 1:
         raise ValueError("generate: every prompt needs at least one token")
-    if max_new_tokens < 0 or temperature < 0.0 or not 0.0 < top_p <= 1.0 or top_k < 0:
-        raise ValueError("generate: need max_new_tokens >= 0, temperature >= 0, 0 < top_p <= 1, top_k >= 0")
+    if sampler not in ("torch", "fused"):
+        raise ValueError(f"generate: sampler must be 'torch' or 'fused', got {sampler!r}")
+    fused = None
+    if sampler == "fused":
+        fused = _fused_params(len(prompts), temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p)
+        if max_new_tokens < 0:
+            raise ValueError("generate: need max_new_tokens >= 0")
+    else:
+        if any(isinstance(v, (list, tuple, torch.Tensor)) for v in (temperature, top_k, top_p, min_p)):
+            raise ValueError('generate: per-prompt sampling parameters need sampler="fused"')
+        if not 0.0 <= min_p <= 1.0:
+            raise ValueError("generate: need 0 <= min_p <= 1")
+        if min_p > 0.0:
+            raise ValueError('generate: min_p needs sampler="fused"')
+        if max_new_tokens < 0 or temperature < 0.0 or not 0.0 < top_p <= 1.0 or top_k < 0:
+            raise ValueError("generate: need max_new_tokens >= 0, temperature >= 0, 0 < top_p <= 1, top_k >= 0")
     longest = max(p.numel() for p in prompts)
     if s_max is None:
         s_max = longest + max_new_tokens
@@ -198,7 +235,12 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
         return [torch.empty(0, dtype=torch.long) for _ in range(n)]
     dev = model.embed_tokens.weight.device
     gen = None
-    if temperature > 0.0:
+    if fused is not None:
+        fused = {k: torch.tensor(v, dtype=torch.int32 if k == "top_k" else torch.float32, device=dev)
+                 for k, v in fused.items()}
+        stream = torch.arange(n, dtype=torch.int64, device=dev)
+        step_t = torch.zeros(n, dtype=torch.int64, device=dev)  # the draw counter, advanced on the device
+    elif temperature > 0.0:
         gen = torch.Generator(device=dev)
         gen.manual_seed(int(seed))
     cache = KVCache(model.config, n, s_max, device=dev, dtype=model.embed_tokens.weight.dtype)
@@ -207,7 +249,11 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     done = torch.zeros(n, dtype=torch.bool, device=dev)
     logits = prefill(model, prompts, cache)
     for step in range(max_new_tokens):
-        nxt = sample_next(logits, temperature, top_k, top_p, gen)
+        if fused is not None:
+            nxt, _ = ops.sample_logits(logits, seed=int(seed), stream=stream, step=step_t, **fused)
+            step_t += 1
+        else:
+            nxt = sample_next(logits, temperature, top_k, top_p, gen)
         out[:, step] = nxt
         count += (~done).long()
         if eos_token_id is not None:

@@ -18,6 +18,7 @@ if not _native.LOADED:  # CPU-only box without a build: host AdamW falls back to
 from .functional import (  # noqa: E402
     add_rms_norm,
     attention,
+    check_sample_scalar,
     decode_attention,
     dropout_add_layer_norm,
     embedding,
@@ -30,6 +31,7 @@ from .functional import (  # noqa: E402
     rms_norm,
     rope,
     rope_tables,
+    sample_logits,
     swiglu,
     swiglu_mlp,
     vocab_parallel_fused_linear_cross_entropy,
@@ -58,4 +60,5 @@ __all__ = [
     "add_rms_norm", "attention", "rope", "embedding", "fused_linear_cross_entropy", "linear", "rms_norm",
     "rope_tables", "swiglu", "swiglu_mlp", "vocab_parallel_fused_linear_cross_entropy", "route_param_grad", "adamw_step",
     "fa_tuning", "layer_norm", "dropout_add_layer_norm", "gelu_mlp", "qk_norm_rope", "kv_cache_append", "decode_attention",
+    "sample_logits",
 ]

@@ -666,6 +666,86 @@ def embedding_bwd_(out, ids, dy):
     out.copy_((out.float() + acc).to(out.dtype))
 
 
+def sample_u(rng):
+    """f32 [n]: the uniform of each row of the int64 [n, 3] tensor {seed, stream, step}:
+    (word 0 of Philox4x32-10({step lo, step hi, stream lo, stream hi}, key = {seed lo, seed hi}) >> 8) * 2^-24,
+    bit-equal to the kernel's draw.  Reads `rng` on the host."""
+    import numpy as np
+
+    g = rng.detach().cpu().numpy().astype(np.int64).view(np.uint64).reshape(-1, 3)
+    lo, hi = g & np.uint64(0xFFFFFFFF), g >> np.uint64(32)
+    w0 = philox4x32_10(lo[:, 2], hi[:, 2], lo[:, 1], hi[:, 1], lo[:, 0], hi[:, 0])[0]
+    u = (w0 >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return torch.from_numpy(u).to(rng.device)
+
+
+def sample_logits(logits, params, top_k, rng, u=None):
+    """The definition of ops.sample_logits in f64, for all rows at once and on the tensors' device
+    (DTG_SAMPLE_FUSED=0 runs this on the GPU).  The distinct values of a row and the masses of their tie
+    groups come from one descending sort: the mass of {x >= t} is the running sum at the last element
+    equal to t, found by searchsorted, which is what torch.unique + a group sum give, without its
+    data-dependent shape."""
+    n, V = logits.shape
+    dev = logits.device
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+    ninf = float("-inf")
+    x = logits.to(torch.float64)
+    x = torch.where(torch.isnan(x), torch.full_like(x, ninf), x)
+    T, top_p, min_p = (params[:, i].to(torch.float64) for i in range(3))
+    k = top_k.to(torch.int64)
+    idx = torch.arange(V, device=dev)
+    M = x.max(1).values
+    first_max = torch.where(x == M[:, None], idx, V).min(1).values
+    n_max = (x == M[:, None]).sum(1)
+    dead, hot = M == ninf, M == float("inf")
+    greedy = ~(T > 0)
+    special = dead | hot | greedy
+    Ms = torch.where(special, torch.zeros_like(M), M)[:, None]
+    Ts = torch.where(special, torch.ones_like(T), T)[:, None]
+    xs = torch.where(special[:, None], torch.zeros_like(x), x)  # special rows: any finite row, overridden below
+    w = torch.where(xs == Ms, torch.ones_like(xs), torch.exp((xs - Ms) / Ts))
+    w = torch.where(xs == ninf, torch.zeros_like(w), w)
+
+    desc, order = xs.sort(1, descending=True)
+    asc = desc.flip(1).contiguous()
+    # t_k: the k-th largest, with multiplicity
+    kth = desc.gather(1, (k - 1).clamp(0, V - 1)[:, None])[:, 0]
+    t_k = torch.where((k > 0) & (k < V), kth, torch.full_like(kth, ninf))
+    in_a = xs >= t_k[:, None]
+    wa = w * in_a
+    z_a = wa.sum(1)
+    # t_p: the largest value t of A with mass {A, x >= t} >= top_p Z_A
+    cs = wa.gather(1, order).cumsum(1)
+    n_ge = V - torch.searchsorted(asc, desc.contiguous(), right=False)  # elements >= each sorted value
+    mass_ge = cs.gather(1, n_ge - 1)
+    ok = (desc >= t_k[:, None]) & (mass_ge >= (top_p * z_a)[:, None])
+    t_p = torch.where(ok, desc, torch.full_like(desc, ninf)).max(1).values
+    t_p = torch.where((top_p > 0) & (top_p < 1), t_p, torch.where(top_p <= 0, Ms[:, 0], torch.full_like(t_p, ninf)))
+    # t_m: w >= min_p
+    t_m = torch.where(min_p > 0, Ms[:, 0] + Ts[:, 0] * torch.log(min_p.clamp_min(1e-300)), torch.full_like(M, ninf))
+    t_m = torch.where(torch.isnan(t_m), torch.full_like(t_m, ninf), t_m)
+    thr = torch.minimum(torch.maximum(torch.maximum(t_k, t_p), t_m), Ms[:, 0])
+    in_k = xs >= thr[:, None]
+    c = (w * in_k).cumsum(1)  # index order
+    z_k = c[:, -1]
+    if u is None:
+        u = sample_u(rng)
+    u = u.to(torch.float64)
+    u = torch.where(u >= 0, u.clamp(max=1.0), torch.zeros_like(u))
+    ids = torch.searchsorted(c, (u * z_k)[:, None], right=True)[:, 0]
+    last = torch.where(in_k, idx, -1).max(1).values
+    ids = torch.where(ids >= V, last, ids)
+    kept = in_k.sum(1)
+
+    ids = torch.where(greedy | hot, first_max, ids)
+    kept = torch.where(greedy, torch.ones_like(kept), kept)
+    kept = torch.where(hot, n_max, kept)
+    ids = torch.where(dead, torch.full_like(ids, -1), ids)
+    kept = torch.where(dead, torch.zeros_like(kept), kept)
+    return ids.to(torch.int64), kept.to(torch.int32)
+
+
 _TUNING = [0, 64]
 
 
@@ -687,5 +767,6 @@ for _name, _fn in list(globals().items()):
         "flash_attn_varlen_bwd", "flash_attn_fwd_drop", "flash_attn_bwd_drop", "flash_attn_bwd_qkv_drop", "philox_rng",
         "flash_attn_bwd_qkv_rope", "flash_attn_tuning", "layernorm_fwd", "dropout_add_layernorm_fwd", "layernorm_bwd",
         "gelu_fwd", "gelu_bwd", "gelu_bwd_t", "qk_norm_rope_fwd_", "qk_norm_rope_bwd_", "kv_cache_append_", "decode_attn",
+        "sample_logits",
     ):
         LIB.impl(_name, _fn, "CPU")

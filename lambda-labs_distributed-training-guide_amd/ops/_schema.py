@@ -44,6 +44,11 @@ _DEFS = [
     # max_len a host upper bound of lens (launch plan only), splits = 0 takes the plan's split count
     "decode_attn(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor rows, Tensor lens, int nq, int nkv, int head_dim, "
     "float scale, int max_len, int window=0, int splits=0) -> Tensor",
+    # fused top-k / top-p / min-p sampling (csrc/kernels/sample.hip): logits [n, V] bf16 / f32 with unit
+    # inner stride; params f32 [n, 3] = temperature, top_p, min_p; top_k int32 [n]; rng int64 [n, 3] =
+    # seed, stream, step of the row's Philox draw; u f32 [n] in [0, 1) replaces that draw.  Returns
+    # (ids int64 [n], kept int32 [n] = size of the set the row was drawn from); nothing is read on the host
+    "sample_logits(Tensor logits, Tensor params, Tensor top_k, Tensor rng, Tensor? u=None) -> (Tensor, Tensor)",
     "swiglu_fwd(Tensor gu) -> Tensor",
     "swiglu_bwd(Tensor dh, Tensor gu) -> Tensor",
     "swiglu_bwd_t(Tensor dh, Tensor gu) -> (Tensor, Tensor, Tensor)",

@@ -606,6 +606,90 @@ def decode_attention(qkv, k_cache, v_cache, rows, lens, nq, nkv, head_dim, max_l
 
 
 # --------------------------------------------------------------------------------------------
+# Sampling: fused top-k / top-p / min-p with a per-sequence Philox draw (csrc/kernels/sample.hip)
+# --------------------------------------------------------------------------------------------
+# DTG_SAMPLE_FUSED=0 composes the same definition from torch ops in f64 on the GPU (the CPU
+# implementation's code run on the device: the kernel's A/B partner; it reads `rng` on the host when no
+# `u` is given); so do, on a GPU, logits dtypes other than bf16 and f32.
+_SAMPLE_FUSED = os.environ.get("DTG_SAMPLE_FUSED", "1") == "1"
+
+_SAMPLE_RULES = {
+    "temperature": (lambda v: v >= 0.0, "temperature >= 0"),
+    "top_k": (lambda v: v >= 0, "top_k >= 0"),
+    "top_p": (lambda v: 0.0 < v <= 1.0, "0 < top_p <= 1"),
+    "min_p": (lambda v: 0.0 <= v <= 1.0, "0 <= min_p <= 1"),
+}
+
+
+def check_sample_scalar(name, v):
+    """The host-side rule of one scalar sampling parameter (ValueError); NaN fails every rule."""
+    ok, text = _SAMPLE_RULES[name]
+    if not ok(v):
+        raise ValueError(f"sample_logits: need {text}, got {name} = {v!r}")
+
+
+def _sample_column(name, v, n, dtype, device):
+    if isinstance(v, torch.Tensor):
+        if v.dim() != 1 or v.shape[0] != n or v.device != device:
+            raise ValueError(f"sample_logits: a tensor {name} must be [{n}] on the logits' device, got "
+                             f"{tuple(v.shape)} on {v.device}")
+        return v.to(dtype)
+    if name in _SAMPLE_RULES:
+        check_sample_scalar(name, v)
+    if dtype == torch.int64:
+        v = (int(v) + 2**63) % 2**64 - 2**63  # the 64 bits of the value, as int64
+    return torch.full((n,), v, dtype=dtype, device=device)
+
+
+@torch.no_grad()
+def sample_logits(logits, temperature=0.0, top_k=0, top_p=1.0, min_p=0.0, seed=0, stream=None, step=0, u=None):
+    """One id per row of `logits` [n, V] -> (ids int64 [n], kept int32 [n]); `kept` is the size of the
+    set the row was drawn from.  One kernel launch; nothing is read on the host.
+
+    Every argument is a Python scalar (validated here, then broadcast) or a device tensor [n] (taken
+    as is, never synced), so rows of one batch may mix greedy and sampled decoding, temperatures and
+    filters.  `stream` defaults to the row index.  Per row, with x = float(logits) (NaN counts as
+    -inf) and M = max x:
+
+      * M = -inf: ids = -1, kept = 0.  M = +inf: the lowest index of a +inf, kept = their number.
+      * temperature T <= 0 or NaN: greedy, the lowest index of M, kept = 1.
+      * else weights w_i = exp((x_i - M) / T) and three value thresholds, each -inf when off:
+          t_k (0 < top_k < V): the top_k-th largest x, with multiplicity; A = {x >= t_k}
+          t_p (0 < top_p < 1): the largest value t of A with sum_{A, x >= t} w >= top_p * sum_A w
+                               (top_p <= 0 keeps the entries equal to M; >= 1 or NaN is off)
+          t_m (min_p > 0):     M + T ln(min_p), i.e. w >= min_p
+        The kept set is K = {x >= max(t_k, t_p, t_m)}: ties at a cut are kept, and the argmax always
+        is.  ids is the smallest i in K whose running sum of w over K in INDEX order exceeds
+        u * sum_K w (the last index of K if rounding leaves none).
+      * u = (word 0 of Philox4x32-10({step lo, step hi, stream lo, stream hi}, key {seed lo, seed hi})
+        >> 8) * 2^-24, or the given `u` (f32 [n] in [0, 1)).
+
+    A row's result depends on that row's logits and parameters alone -- not on the batch size, the
+    row's place in it or the other rows -- and is bitwise the same from run to run."""
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError(f"sample_logits: logits must be [n, V] with V >= 1, got {tuple(logits.shape)}")
+    n, V = logits.shape
+    dev = logits.device
+    col = lambda name, v, dt: _sample_column(name, v, n, dt, dev)  # noqa: E731
+    params = torch.stack([col("temperature", temperature, torch.float32), col("top_p", top_p, torch.float32),
+                          col("min_p", min_p, torch.float32)], 1)
+    k = col("top_k", top_k, torch.int32)
+    if stream is None:
+        stream = torch.arange(n, dtype=torch.int64, device=dev)
+    rng = torch.stack([col("seed", seed, torch.int64), col("stream", stream, torch.int64),
+                       col("step", step, torch.int64)], 1)
+    if u is not None:
+        u = col("u", u, torch.float32)
+    if n and (logits.stride(1) != 1 or (n > 1 and logits.stride(0) < V)):
+        logits = logits.contiguous()
+    if logits.is_cuda and not (_SAMPLE_FUSED and logits.dtype in (torch.bfloat16, torch.float32)):
+        from . import _cpu
+
+        return _cpu.sample_logits(logits, params, k, rng, u)
+    return ops.sample_logits(logits, params, k, rng, u)
+
+
+# --------------------------------------------------------------------------------------------
 # SwiGLU
 # --------------------------------------------------------------------------------------------
 class _SwiGLU(torch.autograd.Function):

@@ -4,6 +4,8 @@
     python tools/sample.py --model-name qwen3-0.6b --num-layers 2 --prompt-ids "1,2,3;4,5"
     python tools/sample.py --model-name llama-3.2-3b --init-from /data/llama-3.2-3b --tokenizer /data/llama-3.2-3b \
         --prompt "The capital of France is" --max-new-tokens 32 --temperature 0.7 --top-p 0.9
+    python tools/sample.py --model-name qwen3-0.6b --prompt-ids "1,2,3;4,5" --temperature 0.8 --top-k 50 --min-p 0.05 \
+        --sampler fused
 
 Weights: `--init-from DIR` (HF safetensors) or `--ckpt DIR` (a sharded checkpoint directory written by
 this trainer); random init otherwise.  Prompts: `--prompt-ids` (sequences separated by ';', ids by
@@ -52,6 +54,11 @@ def main(argv=None):
     ap.add_argument("--temperature", type=float, default=0.0)
     ap.add_argument("--top-k", type=int, default=0)
     ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--min-p", type=float, default=0.0, help="keep ids at least this likely relative to the favourite "
+                    "(needs --sampler fused)")
+    ap.add_argument("--sampler", choices=("torch", "fused"), default="torch",
+                    help="torch: the chain of torch ops, one generator for the batch; fused: one HIP launch per step "
+                    "with a counter-based draw per sequence (different ids for the same seed)")
     ap.add_argument("--eos-token-id", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default=None, help="default: cuda if available, else cpu")
@@ -106,7 +113,7 @@ def main(argv=None):
     sync()
     t0 = time.perf_counter()
     out = dtg.generate(model, prompts, a.max_new_tokens, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p,
-                       eos_token_id=eos, seed=a.seed)
+                       eos_token_id=eos, seed=a.seed, min_p=a.min_p, sampler=a.sampler)
     sync()
     dt = time.perf_counter() - t0
     for i, ids in enumerate(out):
@@ -115,7 +122,7 @@ def main(argv=None):
             print(f"text[{i}]: {tok.decode(ids.tolist())}")
     n = sum(int(o.numel()) for o in out)
     print(json.dumps({"sequences": len(out), "new_tokens": n, "seconds": round(dt, 4),
-                      "tokens_per_s": round(n / dt, 2) if dt > 0 else None, "device": str(dev)}))
+                      "tokens_per_s": round(n / dt, 2) if dt > 0 else None, "device": str(dev), "sampler": a.sampler}))
     return 0
 
 
