@@ -17,6 +17,28 @@
 namespace dtg {
 namespace mlp_act {
 
+// SwiGLU on a fused gate|up row, x = {gate, up}: h = silu(gate) * up.  Lives here because the skinny GEMM's
+// epilogue (skinny_gemm.hip) applies the same functor as swiglu.hip, bit for bit.
+struct SwiGLU {
+  static constexpr int kIn = 2;  // x = {gate, up}
+
+  static __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
+
+  static __device__ __forceinline__ float fwd(const float (&x)[2]) {
+    const float g = x[0], u = x[1];
+    return g * sigmoidf_(g) * u;
+  }
+
+  static __device__ __forceinline__ void bwd(const float (&x)[2], float d, float (&dx)[2], float& h) {
+    const float g = x[0], u = x[1];
+    const float sg = sigmoidf_(g);
+    const float silu = g * sg;
+    dx[1] = d * silu;
+    dx[0] = d * u * sg * (1.f + g * (1.f - sg));
+    h = silu * u;
+  }
+};
+
 template <class Act>
 __global__ void act_fwd_kernel(const uint16_t* __restrict__ x, int64_t x_stride, uint16_t* __restrict__ h, int64_t T,
                                int I) {

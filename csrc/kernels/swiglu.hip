@@ -9,25 +9,7 @@
 
 namespace dtg {
 
-struct SwiGLU {
-  static constexpr int kIn = 2;  // x = {gate, up}
-
-  static __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
-
-  static __device__ __forceinline__ float fwd(const float (&x)[2]) {
-    const float g = x[0], u = x[1];
-    return g * sigmoidf_(g) * u;
-  }
-
-  static __device__ __forceinline__ void bwd(const float (&x)[2], float d, float (&dx)[2], float& h) {
-    const float g = x[0], u = x[1];
-    const float sg = sigmoidf_(g);
-    const float silu = g * sg;
-    dx[1] = d * silu;
-    dx[0] = d * u * sg * (1.f + g * (1.f - sg));
-    h = silu * u;
-  }
-};
+using mlp_act::SwiGLU;
 
 at::Tensor swiglu_fwd(const at::Tensor& gu) { return mlp_act::act_fwd<SwiGLU>(gu, "swiglu_fwd"); }
 at::Tensor swiglu_bwd(const at::Tensor& dh, const at::Tensor& gu) {

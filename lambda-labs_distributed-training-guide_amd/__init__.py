@@ -14,4 +14,8 @@ def __getattr__(name):  # `from dtg import generate` without importing torch at 
         from .models.generation import generate
 
         return generate
+    if name == "GraphedDecode":
+        from .models.decode_graph import GraphedDecode
+
+        return GraphedDecode
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -58,8 +58,23 @@ class KVCache:
         self.max_len = 0
 
 
-def _run_layers(model, x, append_and_attend):
-    """The decoder stack around a caller-supplied attention (qkv -> attention output)."""
+LINEAR_MODES = ("blas", "skinny")
+SKINNY_MAX_ROWS = 16  # = ops.functional.SKINNY_MAX_M: # sequences a decode step with linear="skinny" takes
+
+
+def _check_linear(linear, n=None):
+    if linear not in LINEAR_MODES:
+        raise ValueError(f"linear must be one of {LINEAR_MODES}, got {linear!r}")
+    if linear == "skinny" and n is not None and n > SKINNY_MAX_ROWS:
+        raise ValueError(f'linear="skinny" decodes at most {SKINNY_MAX_ROWS} sequences per step, got {n}')
+
+
+def _run_layers(model, x, append_and_attend, linear="blas"):
+    """The decoder stack around a caller-supplied attention (qkv -> attention output).  linear="skinny"
+    (a decode step of at most 16 rows): the qkv, o, gate_up (+ SwiGLU) and down projections run in
+    ops.skinny_linear instead of hipBLASLt."""
+    if linear == "skinny":
+        return _run_layers_skinny(model, x, append_and_attend)
     res = None
     for i, layer in enumerate(model.layers):
         if res is None:
@@ -75,6 +90,21 @@ def _run_layers(model, x, append_and_attend):
     return x, res
 
 
+def _run_layers_skinny(model, x, append_and_attend):
+    res = None
+    for i, layer in enumerate(model.layers):
+        if res is None:
+            n, res = ops.rms_norm(x, layer.input_layernorm.weight, layer.eps), x
+        else:
+            n, res = ops.add_rms_norm(x, res, layer.input_layernorm.weight, layer.eps)
+        attn, mlp = layer.self_attn, layer.mlp
+        qkv = ops.skinny_linear(n, attn.qkv_proj.weight, getattr(attn.qkv_proj, "bias", None))
+        a = ops.skinny_linear(append_and_attend(i, attn, qkv), attn.o_proj.weight)
+        n2, res = ops.add_rms_norm(a, res, layer.post_attention_layernorm.weight, layer.eps)
+        x = ops.skinny_linear(ops.skinny_linear(n2, mlp.gate_up_proj.weight, act="swiglu"), mlp.down_proj.weight)
+    return x, res
+
+
 def _append(attn, qkv, cache, i, cos, sin, pos, rows, pos_max):
     """RoPE (after the per-head norm for Qwen3, whose fused pass ropes itself) and the cache write.
     `pos_max`: the host's largest position of the call, checked by the op (rows were checked by _rows)."""
@@ -86,8 +116,10 @@ def _append(attn, qkv, cache, i, cos, sin, pos, rows, pos_max):
                                pos_max=pos_max)
 
 
-def _last_logits(model, x, res):
+def _last_logits(model, x, res, linear="blas"):
     h, _ = ops.add_rms_norm(x, res, model.norm.weight, model.config.rms_norm_eps)
+    if linear == "skinny":
+        return ops.skinny_linear(h, model.lm_head_weight())
     return ops.linear(h, model.lm_head_weight())
 
 
@@ -132,30 +164,64 @@ def prefill(model, prompts: Sequence[torch.Tensor], cache: KVCache, rows: Option
     return _last_logits(model, x[last], res[last])
 
 
+def _decode_body(model, tokens, cache, rows_t, plan_len, linear):
+    """One decode step on device tensors only (`tokens` [n] ids, `rows_t` [n] int32 cache rows): nothing is
+    built from host data and nothing is read back, so a HIP graph can record it.  `plan_len` is the host
+    length of the attention's launch plan and of the append's position check.  Advances cache.lens, not the
+    host's cache.max_len; returns the logits [n, V]."""
+    dev = cache.lens.device
+    pos = cache.lens[rows_t.long()].long()
+    new_lens = (pos + 1).to(torch.int32)
+    cos, sin = model._rope_tables(cache.s_max, dev)
+
+    def attend(i, attn, qkv):
+        qkv = _append(attn, qkv, cache, i, cos, sin, pos, rows_t, plan_len - 1)
+        return ops.decode_attention(qkv, cache.k[i], cache.v[i], rows_t, new_lens, attn.nq, attn.nkv, attn.d, plan_len,
+                                    window=attn.window)
+
+    x, res = _run_layers(model, ops.embedding(tokens, model.embed_tokens.weight), attend, linear)
+    cache.lens[rows_t.long()] = new_lens
+    return _last_logits(model, x, res, linear)
+
+
 @torch.no_grad()
-def decode_step(model, tokens: torch.Tensor, cache: KVCache, rows: Optional[Sequence[int]] = None):
+def decode_step(model, tokens: torch.Tensor, cache: KVCache, rows: Optional[Sequence[int]] = None,
+                linear: str = "blas", plan_len: Optional[int] = None):
     """One new token per active sequence (`tokens` [n], for cache rows `rows`, default 0..n-1): appends
-    it at the row's current length and returns the next-token logits [n, V]."""
+    it at the row's current length and returns the next-token logits [n, V].
+
+    linear="skinny": the five projections of the step (qkv, o, gate_up with its SwiGLU, down, LM head)
+    run in `ops.skinny_linear` (at most 16 sequences).  `plan_len`: the host length the attention's
+    launch plan is made for, cache.max_len + 1 <= plan_len <= S_max (default cache.max_len + 1, the
+    tightest); a captured step is planned for its whole length bucket, and an eager step given the same
+    `plan_len` runs the same launches."""
     _check_model(model)
     if cache.max_len + 1 > cache.s_max:
         raise ValueError(f"decode_step: the cache is full (S_max = {cache.s_max})")
     dev = cache.lens.device
     tokens = tokens.reshape(-1).to(dev)
-    rows_t = _rows(cache, tokens.numel(), rows, dev)
-    pos = cache.lens[rows_t.long()].long()
-    new_lens = (pos + 1).to(torch.int32)
-    cos, sin = model._rope_tables(cache.s_max, dev)
+    _check_linear(linear, tokens.numel())
     max_len = cache.max_len + 1
-
-    def attend(i, attn, qkv):
-        qkv = _append(attn, qkv, cache, i, cos, sin, pos, rows_t, max_len - 1)
-        return ops.decode_attention(qkv, cache.k[i], cache.v[i], rows_t, new_lens, attn.nq, attn.nkv, attn.d, max_len,
-                                    window=attn.window)
-
-    x, res = _run_layers(model, ops.embedding(tokens, model.embed_tokens.weight), attend)
-    cache.lens[rows_t.long()] = new_lens
+    if plan_len is None:
+        plan_len = max_len
+    if not max_len <= int(plan_len) <= cache.s_max:
+        raise ValueError(f"decode_step: plan_len {plan_len} outside [cache.max_len + 1 = {max_len}, S_max = {cache.s_max}]")
+    rows_t = _rows(cache, tokens.numel(), rows, dev)
+    logits = _decode_body(model, tokens, cache, rows_t, int(plan_len), linear)
     cache.max_len = max_len
-    return _last_logits(model, x, res)
+    return logits
+
+
+def decode_bucket(length: int, s_max: int) -> int:
+    """The length bucket a captured decode step is planned for: the smallest of 256, 512, 1024, ... that is
+    >= `length`, capped at `s_max`.  256 is the decode plan's smallest chunk (decode::kMinChunk): below it
+    the plan never splits, so shorter buckets would only add graphs."""
+    if not 0 <= length <= s_max:
+        raise ValueError(f"decode_bucket: length {length} outside [0, S_max = {s_max}]")
+    b = 256
+    while b < length:
+        b *= 2
+    return min(b, int(s_max))
 
 
 def sample_next(logits, temperature=0.0, top_k=0, top_p=1.0, generator=None):
@@ -191,7 +257,8 @@ def _fused_params(n, **given):
 @torch.no_grad()
 def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              top_p: float = 1.0, eos_token_id: Optional[int] = None, seed: int = 0, s_max: Optional[int] = None,
-             min_p: float = 0.0, sampler: str = "torch") -> List[torch.Tensor]:
+             min_p: float = 0.0, sampler: str = "torch", linear: str = "blas", decode="eager",
+             bucketed: bool = False) -> List[torch.Tensor]:
     """Continue every prompt by up to `max_new_tokens` ids; returns the new ids of each sequence (1-D
     int64 tensors on the CPU), ending with `eos_token_id` where the sequence produced it.
 
@@ -204,13 +271,34 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     done mask lives on the device and is read on the host every HOST_CHECK_EVERY steps only; finished
     sequences keep running (their ids are discarded) until all are done or the budget is spent.
     `s_max` sizes the cache (default: longest prompt + max_new_tokens); prompt + max_new_tokens beyond
-    it is an error."""
+    it is an error.
+
+    linear="skinny": the decode steps' projections run in `ops.skinny_linear` (at most 16 prompts; the
+    prefill keeps hipBLASLt).  decode="graph" (GPU only): the decode loop is captured into one HIP graph
+    per length bucket (`decode_bucket`) and replayed, see models/decode_graph.py; sampling then needs
+    sampler="fused", whose draw counter lives on the device.  `decode` may also be a `GraphedDecode`
+    built for this model, batch size and `s_max`: its graphs and cache are reused.  decode="eager" with
+    `bucketed=True` runs the eager loop with the launch plans of the captured one (plan_len = the
+    bucket): with linear="skinny" the two loops return the same ids bit for bit."""
     _check_model(model)
     prompts = [p.reshape(-1) for p in prompts]
     if not prompts or min(p.numel() for p in prompts) < 1:
         raise ValueError("generate: every prompt needs at least one token")
     if sampler not in ("torch", "fused"):
         raise ValueError(f"generate: sampler must be 'torch' or 'fused', got {sampler!r}")
+    _check_linear(linear, len(prompts))
+    graphed = not isinstance(decode, str)
+    if not graphed and decode not in ("eager", "graph"):
+        raise ValueError(f"generate: decode must be 'eager', 'graph' or a GraphedDecode, got {decode!r}")
+    graphed = graphed or decode == "graph"
+    if graphed:
+        sampled = any(float(t) > 0.0 for t in (temperature.tolist() if isinstance(temperature, torch.Tensor) else
+                                               temperature if isinstance(temperature, (list, tuple)) else [temperature]))
+        if sampled and sampler != "fused":
+            raise ValueError('generate: decode="graph" with temperature > 0 needs sampler="fused" (the torch sampler '
+                             "draws from a host-side generator, which a captured step cannot advance)")
+        if model.embed_tokens.weight.device.type != "cuda":
+            raise ValueError('generate: decode="graph" needs a GPU (HIP-graph capture)')
     fused = None
     if sampler == "fused":
         fused = _fused_params(len(prompts), temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p)
@@ -234,6 +322,11 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     if max_new_tokens == 0:
         return [torch.empty(0, dtype=torch.long) for _ in range(n)]
     dev = model.embed_tokens.weight.device
+    if graphed:
+        from .decode_graph import GraphedDecode
+
+        gd = decode if isinstance(decode, GraphedDecode) else GraphedDecode(model, n, s_max, linear=linear)
+        return gd.run(prompts, max_new_tokens, fused, seed, eos_token_id, s_max=s_max, linear=linear)
     gen = None
     if fused is not None:
         fused = {k: torch.tensor(v, dtype=torch.int32 if k == "top_k" else torch.float32, device=dev)
@@ -261,6 +354,7 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
             if (step + 1) % HOST_CHECK_EVERY == 0 and bool(done.all()):
                 break
         if step + 1 < max_new_tokens:
-            logits = decode_step(model, nxt, cache)
+            plan_len = decode_bucket(cache.max_len + 1, s_max) if bucketed else None
+            logits = decode_step(model, nxt, cache, linear=linear, plan_len=plan_len)
     out, count = out.cpu(), count.tolist()
     return [out[i, : count[i]].clone() for i in range(n)]

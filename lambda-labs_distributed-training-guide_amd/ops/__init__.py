@@ -32,6 +32,7 @@ from .functional import (  # noqa: E402
     rope,
     rope_tables,
     sample_logits,
+    skinny_linear,
     swiglu,
     swiglu_mlp,
     vocab_parallel_fused_linear_cross_entropy,
@@ -60,5 +61,5 @@ __all__ = [
     "add_rms_norm", "attention", "rope", "embedding", "fused_linear_cross_entropy", "linear", "rms_norm",
     "rope_tables", "swiglu", "swiglu_mlp", "vocab_parallel_fused_linear_cross_entropy", "route_param_grad", "adamw_step",
     "fa_tuning", "layer_norm", "dropout_add_layer_norm", "gelu_mlp", "qk_norm_rope", "kv_cache_append", "decode_attention",
-    "sample_logits",
+    "sample_logits", "skinny_linear",
 ]

@@ -150,6 +150,39 @@ def swiglu_fwd(gu):
     return (F.silu(g) * u).to(gu.dtype)
 
 
+SKINNY_MAX_M = 16
+
+
+def skinny_linear(x, w, bias, act=0):
+    """y = x @ w^T (+ bias) at 1 <= M <= 16 rows, f32 sums, one rounding; act = 1: the gate and up halves
+    of that (rounded) product through swiglu_fwd, [M, N / 2] (csrc/kernels/skinny_gemm.hip).  Refuses
+    what the kernel refuses."""
+    name = "dtg: skinny_linear"
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        raise RuntimeError(f"{name}: x and w must be bf16 tensors")
+    if act not in (0, 1):
+        raise RuntimeError(f"{name}: act must be 0 (none) or 1 (SwiGLU)")
+    if x.dim() != 2 or not 1 <= x.shape[0] <= SKINNY_MAX_M:
+        raise RuntimeError(f"{name}: x must be [M, K] with 1 <= M <= {SKINNY_MAX_M}")
+    K = x.shape[1]
+    if K % 8:
+        raise RuntimeError(f"{name}: K must be a multiple of 8")
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+        raise RuntimeError(f"{name}: x must have unit inner stride and 16-B aligned rows")
+    if w.dim() != 2 or w.shape[1] != K or w.shape[0] < 1 or not w.is_contiguous():
+        raise RuntimeError(f"{name}: w must be a contiguous [N, K] on x's device")
+    N = w.shape[0]
+    if act and N % 2:
+        raise RuntimeError(f"{name}: the SwiGLU epilogue needs an even N (gate rows, then up rows)")
+    y = x.float() @ w.float().t()
+    if bias is not None:
+        if bias.dtype != torch.bfloat16 or bias.dim() != 1 or bias.shape[0] != N or not bias.is_contiguous():
+            raise RuntimeError(f"{name}: bias must be a contiguous bf16 [N]")
+        y = y + bias.float()
+    y = y.to(x.dtype)
+    return swiglu_fwd(y) if act else y
+
+
 def swiglu_bwd(dh, gu):
     inter = gu.shape[1] // 2
     g, u, d = gu[:, :inter].float(), gu[:, inter:].float(), dh.float()
@@ -767,6 +800,6 @@ for _name, _fn in list(globals().items()):
         "flash_attn_varlen_bwd", "flash_attn_fwd_drop", "flash_attn_bwd_drop", "flash_attn_bwd_qkv_drop", "philox_rng",
         "flash_attn_bwd_qkv_rope", "flash_attn_tuning", "layernorm_fwd", "dropout_add_layernorm_fwd", "layernorm_bwd",
         "gelu_fwd", "gelu_bwd", "gelu_bwd_t", "qk_norm_rope_fwd_", "qk_norm_rope_bwd_", "kv_cache_append_", "decode_attn",
-        "sample_logits",
+        "sample_logits", "skinny_linear",
     ):
         LIB.impl(_name, _fn, "CPU")

@@ -49,6 +49,10 @@ _DEFS = [
     # seed, stream, step of the row's Philox draw; u f32 [n] in [0, 1) replaces that draw.  Returns
     # (ids int64 [n], kept int32 [n] = size of the set the row was drawn from); nothing is read on the host
     "sample_logits(Tensor logits, Tensor params, Tensor top_k, Tensor rng, Tensor? u=None) -> (Tensor, Tensor)",
+    # decode-step projection (csrc/kernels/skinny_gemm.hip): y = x @ w^T (+ bias) for x bf16 [M, K], 1 <= M <= 16
+    # (unit inner stride, 16-B aligned rows), w bf16 [N, K] contiguous, K % 8 == 0, f32 accumulation, one
+    # rounding; act = 1: w = gate rows then up rows, returns swiglu_fwd of that product, [M, N / 2]
+    "skinny_linear(Tensor x, Tensor w, Tensor? bias, int act=0) -> Tensor",
     "swiglu_fwd(Tensor gu) -> Tensor",
     "swiglu_bwd(Tensor dh, Tensor gu) -> Tensor",
     "swiglu_bwd_t(Tensor dh, Tensor gu) -> (Tensor, Tensor, Tensor)",

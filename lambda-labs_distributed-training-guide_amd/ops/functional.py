@@ -708,6 +708,45 @@ def swiglu(gu):
     return _SwiGLU.apply(gu)
 
 
+# --------------------------------------------------------------------------------------------
+# Skinny GEMM: the decode step's projections at M <= 16 rows (csrc/kernels/skinny_gemm.hip)
+# --------------------------------------------------------------------------------------------
+# Inference only (no autograd).  DTG_SKINNY_FUSED=0 composes the same function from torch.mm / addmm
+# (hipBLASLt) and ops.swiglu: the kernel's A/B partner; so do, on a GPU, dtypes other than bf16.
+_SKINNY_FUSED = os.environ.get("DTG_SKINNY_FUSED", "1") == "1"
+SKINNY_MAX_M = 16  # rows the kernel is instantiated for
+
+
+@torch.no_grad()
+def skinny_linear(x, w, b=None, act=None):
+    """y = x @ w^T (+ b) for 1 <= M <= 16 rows of x [M, K]: the weight-streaming kernel of the decode
+    step.  `w` is [N, K] (the nn.Linear layout), `b` [N] or None.  act = "swiglu" (or 1): `w` holds the
+    gate rows, then the up rows (LlamaMLP.gate_up_proj); the result is swiglu(x @ w^T (+ b)), [M, N / 2],
+    bitwise what `swiglu(skinny_linear(x, w, b))` returns, in one launch.  f32 accumulation in a fixed
+    order that does not depend on M: a row's result is the same alone and inside a batch."""
+    if act not in (None, 0, 1, "swiglu"):
+        raise ValueError(f"skinny_linear: act must be None or 'swiglu', got {act!r}")
+    act = 1 if act in (1, "swiglu") else 0
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"skinny_linear: x [M, K] and w [N, K] do not match: {tuple(x.shape)}, {tuple(w.shape)}")
+    if x.shape[0] > SKINNY_MAX_M:
+        raise ValueError(f"skinny_linear: M = {x.shape[0]} rows exceed the kernel's limit of {SKINNY_MAX_M}")
+    if act and w.shape[0] % 2:
+        raise ValueError(f"skinny_linear: the SwiGLU epilogue needs an even N, got {w.shape[0]}")
+    if b is not None:
+        b = b.reshape(-1)
+    if x.is_cuda and not (_SKINNY_FUSED and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16):
+        y = torch.mm(x, w.t()) if b is None else torch.addmm(b, x, w.t())
+        if not act:
+            return y
+        inter = w.shape[0] // 2
+        if inter % 8 == 0:
+            return ops.swiglu_fwd(y)
+        g, u = y[:, :inter].float(), y[:, inter:].float()  # widths the swiglu kernel does not take
+        return (F.silu(g) * u).to(y.dtype)
+    return ops.skinny_linear(x, w, b, act)
+
+
 def _mlp_backward(act, x, w1, w2, a, dy, b1=None, b2=None):
     """Backward of y = act(x @ w1^T (+ b1)) @ w2^T (+ b2) from the saved pre-activation a; `act`
     names the operators {act}_fwd / _bwd / _bwd_t.  Returns dx, dw1, dw2, db1, db2.

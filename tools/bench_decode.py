@@ -49,7 +49,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--min-ms", type=float, default=200.0)
     ap.add_argument("--md", default=None, help="also write the table as markdown here")
+    ap.add_argument("--batches", default=None, help="comma-separated batch sizes instead of 1,8,64")
+    ap.add_argument("--lengths", default=None, help="comma-separated cache lengths instead of 1024,8192,32768")
+    ap.add_argument("--true-len", type=int, default=None, help="every sequence is this long while the launch plan is "
+                    "made for the cache length (max_len): what planning for a whole length bucket costs")
     a = ap.parse_args()
+    batches = BATCHES if a.batches is None else tuple(int(v) for v in a.batches.split(","))
+    lengths = LENGTHS if a.lengths is None else tuple(int(v) for v in a.lengths.split(","))
     import torch
 
     if not torch.cuda.is_available():
@@ -60,14 +66,15 @@ def main():
 
     dev = torch.device("cuda:0")
     rows_out = []
-    for B in BATCHES:
-        for L in LENGTHS:
+    for B in batches:
+        for L in lengths:
             g = torch.Generator(device=dev).manual_seed(B * 100003 + L)
             qkv = torch.randn(B, (NQ + 2 * NKV) * D, device=dev, generator=g).to(torch.bfloat16)
             kc = torch.randn(B, NKV, L, D, device=dev, generator=g).to(torch.bfloat16)
             vc = torch.randn(B, NKV, L, D, device=dev, generator=g).to(torch.bfloat16)
             rows = torch.arange(B, dtype=torch.int32, device=dev)
-            lens = torch.full((B,), L, dtype=torch.int32, device=dev)
+            n_keys = L if a.true_len is None else min(a.true_len, L)
+            lens = torch.full((B,), n_keys, dtype=torch.int32, device=dev)
 
             def call():
                 return ops.decode_attention(qkv, kc, vc, rows, lens, NQ, NKV, D, L)
@@ -80,8 +87,8 @@ def main():
                 res[fused] = min(res.get(fused, t), t)
             functional._DECODE_FUSED = True
             diff = (outs[True].float() - outs[False].float()).abs().max().item()
-            nbytes = 2 * B * NKV * L * D * 2
-            r = {"batch": B, "len": L, "kernel_us": round(res[True] * 1e3, 1), "composed_us": round(res[False] * 1e3, 1),
+            nbytes = 2 * B * NKV * n_keys * D * 2
+            r = {"batch": B, "len": L, "keys": n_keys, "kernel_us": round(res[True] * 1e3, 1), "composed_us": round(res[False] * 1e3, 1),
                  "kernel_GBps": round(nbytes / res[True] / 1e6, 1), "composed_GBps": round(nbytes / res[False] / 1e6, 1),
                  "speedup": round(res[False] / res[True], 2), "max_abs_diff": round(diff, 5)}
             print(json.dumps(r), flush=True)

@@ -6,6 +6,8 @@
         --prompt "The capital of France is" --max-new-tokens 32 --temperature 0.7 --top-p 0.9
     python tools/sample.py --model-name qwen3-0.6b --prompt-ids "1,2,3;4,5" --temperature 0.8 --top-k 50 --min-p 0.05 \
         --sampler fused
+    python tools/sample.py --model-name qwen3-0.6b --prompt-ids "1,2,3;4,5" --max-new-tokens 256 --linear skinny \
+        --decode graph
 
 Weights: `--init-from DIR` (HF safetensors) or `--ckpt DIR` (a sharded checkpoint directory written by
 this trainer); random init otherwise.  Prompts: `--prompt-ids` (sequences separated by ';', ids by
@@ -59,6 +61,11 @@ def main(argv=None):
     ap.add_argument("--sampler", choices=("torch", "fused"), default="torch",
                     help="torch: the chain of torch ops, one generator for the batch; fused: one HIP launch per step "
                     "with a counter-based draw per sequence (different ids for the same seed)")
+    ap.add_argument("--linear", choices=("blas", "skinny"), default="blas",
+                    help="decode-step projections: hipBLASLt, or the skinny-GEMM HIP kernel (at most 16 prompts)")
+    ap.add_argument("--decode", choices=("eager", "graph"), default="eager",
+                    help="graph: capture the decode step into one HIP graph per length bucket and replay it (GPU; "
+                    "sampling then needs --sampler fused)")
     ap.add_argument("--eos-token-id", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default=None, help="default: cuda if available, else cpu")
@@ -113,7 +120,7 @@ def main(argv=None):
     sync()
     t0 = time.perf_counter()
     out = dtg.generate(model, prompts, a.max_new_tokens, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p,
-                       eos_token_id=eos, seed=a.seed, min_p=a.min_p, sampler=a.sampler)
+                       eos_token_id=eos, seed=a.seed, min_p=a.min_p, sampler=a.sampler, linear=a.linear, decode=a.decode)
     sync()
     dt = time.perf_counter() - t0
     for i, ids in enumerate(out):
@@ -122,7 +129,8 @@ def main(argv=None):
             print(f"text[{i}]: {tok.decode(ids.tolist())}")
     n = sum(int(o.numel()) for o in out)
     print(json.dumps({"sequences": len(out), "new_tokens": n, "seconds": round(dt, 4),
-                      "tokens_per_s": round(n / dt, 2) if dt > 0 else None, "device": str(dev), "sampler": a.sampler}))
+                      "tokens_per_s": round(n / dt, 2) if dt > 0 else None, "device": str(dev), "sampler": a.sampler,
+                      "linear": a.linear, "decode": a.decode}))
     return 0
 
 
