@@ -17,41 +17,9 @@
 
 namespace dtg {
 
-template <typename T>
-__device__ __forceinline__ float ld(const T* p, int64_t i);
-template <>
-__device__ __forceinline__ float ld<uint16_t>(const uint16_t* p, int64_t i) { return bf2f(p[i]); }
-template <>
-__device__ __forceinline__ float ld<float>(const float* p, int64_t i) { return p[i]; }
-template <typename T>
-__device__ __forceinline__ void st(T* p, int64_t i, float v);
-template <>
-__device__ __forceinline__ void st<uint16_t>(uint16_t* p, int64_t i, float v) { p[i] = f2bf(v); }
-template <>
-__device__ __forceinline__ void st<float>(float* p, int64_t i, float v) { p[i] = v; }
-
 struct AdamHyper {
   float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, grad_scale;
 };
-
-template <typename T>
-__device__ __forceinline__ void ld8(const T* p, float* o);
-template <>
-__device__ __forceinline__ void ld8<uint16_t>(const uint16_t* p, float* o) { load8(p, o); }
-template <>
-__device__ __forceinline__ void ld8<float>(const float* p, float* o) {
-  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-  o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-}
-template <typename T>
-__device__ __forceinline__ void st8(T* p, const float* v);
-template <>
-__device__ __forceinline__ void st8<uint16_t>(uint16_t* p, const float* v) { store8(p, v); }
-template <>
-__device__ __forceinline__ void st8<float>(float* p, const float* v) {
-  reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-  reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-}
 
 __device__ __forceinline__ void adam_elem(float& pv, float gv, float& mv, float& vv, const AdamHyper& h,
                                           float step_size, float decay) {
@@ -96,10 +64,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(uint16_t* __restrict__ p, fl
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t k = i + u * stride;
-        if (MASTER) ld8<float>(master + k, pv[u]); else load8(p + k, pv[u]);
-        ld8<GT>(g + k, gv[u]);
-        ld8<ST>(m + k, mv[u]);
-        ld8<ST>(v + k, vv[u]);
+        if (MASTER) ld8(master + k, pv[u]); else load8(p + k, pv[u]);
+        ld8(g + k, gv[u]);
+        ld8(m + k, mv[u]);
+        ld8(v + k, vv[u]);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -107,33 +75,33 @@ __global__ __launch_bounds__(256) void adamw_kernel(uint16_t* __restrict__ p, fl
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           adam_elem(pv[u][j], gv[u][j] * h.grad_scale, mv[u][j], vv[u][j], h, step_size, decay);
-        st8<ST>(m + k, mv[u]);
-        st8<ST>(v + k, vv[u]);
-        if (MASTER) st8<float>(master + k, pv[u]);
+        st8(m + k, mv[u]);
+        st8(v + k, vv[u]);
+        if (MASTER) st8(master + k, pv[u]);
         store8(p + k, pv[u]);
       }
     }
     for (; i < n; i += stride) {
       float pv[8], gv[8], mv[8], vv[8];
-      if (MASTER) ld8<float>(master + i, pv); else load8(p + i, pv);
-      ld8<GT>(g + i, gv);
-      ld8<ST>(m + i, mv);
-      ld8<ST>(v + i, vv);
+      if (MASTER) ld8(master + i, pv); else load8(p + i, pv);
+      ld8(g + i, gv);
+      ld8(m + i, mv);
+      ld8(v + i, vv);
 #pragma unroll
       for (int j = 0; j < 8; ++j) adam_elem(pv[j], gv[j] * h.grad_scale, mv[j], vv[j], h, step_size, decay);
-      st8<ST>(m + i, mv);
-      st8<ST>(v + i, vv);
-      if (MASTER) st8<float>(master + i, pv);
+      st8(m + i, mv);
+      st8(v + i, vv);
+      if (MASTER) st8(master + i, pv);
       store8(p + i, pv);
     }
   } else {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
       float pv = MASTER ? master[i] : bf2f(p[i]);
-      float mv = ld<ST>(m, i), vv = ld<ST>(v, i);
-      adam_elem(pv, ld<GT>(g, i) * h.grad_scale, mv, vv, h, step_size, decay);
-      st<ST>(m, i, mv);
-      st<ST>(v, i, vv);
+      float mv = ld(m, i), vv = ld(v, i);
+      adam_elem(pv, ld(g, i) * h.grad_scale, mv, vv, h, step_size, decay);
+      st(m, i, mv);
+      st(v, i, vv);
       if (MASTER) master[i] = pv;
       p[i] = f2bf(pv);
     }
@@ -319,9 +287,9 @@ __global__ __launch_bounds__(TC) void adamw_t_reg_kernel(uint16_t* __restrict__ 
         vv[j] = vr[i][j];
         adam_elem(pv[j], gr[i][j] * h.grad_scale, mv[j], vv[j], h, step_size, decay);
       }
-      st8<ST>(m + k, mv);
-      st8<ST>(v + k, vv);
-      if (MASTER) st8<float>(master + k, pv);
+      st8(m + k, mv);
+      st8(v + k, vv);
+      if (MASTER) st8(master + k, pv);
 #pragma unroll
       for (int j = 0; j < 8; ++j) pb[i][j] = f2bf(pv[j]);
       *reinterpret_cast<u16x8*>(p + k) = pb[i];

@@ -38,10 +38,13 @@ __device__ __forceinline__ uint16_t f2bf(float f) {
   return __builtin_bit_cast(uint16_t, b);
 }
 
-__device__ __forceinline__ void load8(const uint16_t* p, float* out) {
-  u16x8 v = *reinterpret_cast<const u16x8*>(p);
+__device__ __forceinline__ void widen8(const u16x8& v, float* out) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) out[i] = bf2f(v[i]);
+}
+
+__device__ __forceinline__ void load8(const uint16_t* p, float* out) {
+  widen8(*reinterpret_cast<const u16x8*>(p), out);
 }
 
 __device__ __forceinline__ void store8(uint16_t* p, const float* in) {
@@ -51,11 +54,39 @@ __device__ __forceinline__ void store8(uint16_t* p, const float* in) {
   *reinterpret_cast<u16x8*>(p) = v;
 }
 
+// 8 x f32 as two 16-byte accesses (p is 16-byte aligned).
+__device__ __forceinline__ void load8f(const float* p, float* out) {
+  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
+  out[0] = a.x; out[1] = a.y; out[2] = a.z; out[3] = a.w;
+  out[4] = b.x; out[5] = b.y; out[6] = b.z; out[7] = b.w;
+}
+
+__device__ __forceinline__ void store8f(float* p, const float* v) {
+  reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
+  reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
+}
+
+// One element / eight elements of a bf16 (as uint16_t) or f32 buffer, as f32.
+__device__ __forceinline__ float ld(const uint16_t* p, int64_t i) { return bf2f(p[i]); }
+__device__ __forceinline__ float ld(const float* p, int64_t i) { return p[i]; }
+__device__ __forceinline__ void st(uint16_t* p, int64_t i, float v) { p[i] = f2bf(v); }
+__device__ __forceinline__ void st(float* p, int64_t i, float v) { p[i] = v; }
+__device__ __forceinline__ void ld8(const uint16_t* p, float* o) { load8(p, o); }
+__device__ __forceinline__ void ld8(const float* p, float* o) { load8f(p, o); }
+__device__ __forceinline__ void st8(uint16_t* p, const float* v) { store8(p, v); }
+__device__ __forceinline__ void st8(float* p, const float* v) { store8f(p, v); }
+
+// Butterfly sum over aligned groups of W lanes (a power of two, at most the wave).
+template <int W, typename T>
+__device__ __forceinline__ T lanes_sum(T v) {
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+  return v;
+}
+
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
+  return lanes_sum<kWave>(v);
 }
 
 template <typename T>

@@ -5,12 +5,12 @@
 // keys of one kv head are contiguous along the sequence, so a workgroup streams its chunk linearly.
 //
 // kv_cache_append_: per token t of the fused projection output qkv [T, (nq + 2 nkv) D], rotates the
-// q and k heads in place at pos[t] with rope.hip's pairing (i, i + D/2), operation order and single
-// rounding (the roped bits equal rope_'s), then copies the roped k and the v heads to
+// q and k heads in place at pos[t] with the pairing (i, i + D/2), operation order (rope_common.h) and
+// single rounding of rope_ (the roped bits equal rope_'s), then copies the roped k and the v heads to
 // cache[rows[t], :, pos[t], :].  Empty tables = already roped (Qwen3 ropes in qk_norm_rope_fwd_):
 // copy only.  A token whose pos / rows lie outside the cache (or, when roping, whose pos lies past
-// the tables) is skipped entirely.  Thread mapping as rope.hip: one thread per (token, head, 8-pair
-// group), two 16-B accesses each way.
+// the tables) is skipped entirely.  Thread mapping as rope_common.h: one thread per (token, head,
+// 8-pair group), two 16-B accesses each way.
 //
 // decode_attn: grid (sequence, kv head, split), launched flattened.  A workgroup (4 waves) serves all
 // G = nq / nkv query heads of its kv head over its chunk of keys, so K and V are read once per
@@ -25,21 +25,14 @@
 // max = -inf, sum = 0; every exp(m - m_new) is guarded by m == -inf, so the empty partial
 // contributes 0 instead of exp(-inf + inf) = NaN.  Keys outside the attended range are never
 // loaded (the cache may hold anything there, NaN included).
-#include "common.h"
 #include "decode_attn_plan.h"
+#include "rope_common.h"
 
 #include <ATen/hip/HIPContext.h>
 
 namespace dtg {
 
 namespace {
-
-template <int W>
-__device__ __forceinline__ float lanes_sum(float v) {
-#pragma unroll
-  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
 
 // exp(m - m_new) of a running max that may still be -inf (nothing seen): weight 0, never NaN
 __device__ __forceinline__ float rescale(float m, float m_new) { return m == -INFINITY ? 0.f : __expf(m - m_new); }
@@ -51,51 +44,35 @@ __global__ __launch_bounds__(256) void kv_append_kernel(
     const int64_t* __restrict__ pos, const int32_t* __restrict__ rows, int nq, int nkv, int64_t T, int64_t rows_max,
     int64_t S_max) {
   constexpr int HALF = D / 2;
-  constexpr int GROUPS = HALF / 8;
   const int nh = nq + 2 * nkv;
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= T * nh * GROUPS) return;
-  const int grp = gid % GROUPS;
-  const int64_t th = gid / GROUPS;
-  const int head = th % nh;
-  const int64_t tok = th / nh;
-  const int64_t p = pos[tok];
-  const int64_t r = rows[tok];
+  if (gid >= rope::items(T, nh, D)) return;
+  const rope::Item<D> it(gid, nh);
+  const int64_t p = pos[it.tok];
+  const int64_t r = rows[it.tok];
   if (p < 0 || p >= S_max || r < 0 || r >= rows_max) return;
   if (ROPE && p >= max_pos) return;
-  uint16_t* base = qkv + tok * row_stride + (int64_t)head * D + grp * 8;
+  uint16_t* base = it.in(qkv, row_stride);
   u16x8 b1 = *reinterpret_cast<const u16x8*>(base);
   u16x8 b2 = *reinterpret_cast<const u16x8*>(base + HALF);
-  if (ROPE && head < nq + nkv) {
-    float x1[8], x2[8];
+  if (ROPE && it.head < nq + nkv) {
+    float x1[8], x2[8], c[8], s[8];
+    widen8(b1, x1);
+    widen8(b2, x2);
+    rope::load_cs<D>(cos_t, sin_t, p, it.grp, c, s);
+    rope::rotate(x1, x2, c, s, x1, x2);  // rope_kernel's call: the same bits
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      x1[j] = bf2f(b1[j]);
-      x2[j] = bf2f(b2[j]);
-    }
-    const float4* cp = reinterpret_cast<const float4*>(cos_t + p * HALF + grp * 8);
-    const float4* sp = reinterpret_cast<const float4*>(sin_t + p * HALF + grp * 8);
-    float4 c0 = cp[0], c1 = cp[1], s0 = sp[0], s1 = sp[1];
-    float c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-    float s[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-    float o1[8], o2[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {  // rope.hip's expressions: the same bits
-      o1[j] = x1[j] * c[j] - x2[j] * s[j];
-      o2[j] = x2[j] * c[j] + x1[j] * s[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      b1[j] = f2bf(o1[j]);
-      b2[j] = f2bf(o2[j]);
+      b1[j] = f2bf(x1[j]);
+      b2[j] = f2bf(x2[j]);
     }
     *reinterpret_cast<u16x8*>(base) = b1;
     *reinterpret_cast<u16x8*>(base + HALF) = b2;
   }
-  if (head >= nq) {
-    const bool is_k = head < nq + nkv;
-    const int kvh = is_k ? head - nq : head - nq - nkv;
-    uint16_t* dst = (is_k ? kc : vc) + ((r * nkv + kvh) * S_max + p) * D + grp * 8;
+  if (it.head >= nq) {
+    const bool is_k = it.head < nq + nkv;
+    const int kvh = is_k ? it.head - nq : it.head - nq - nkv;
+    uint16_t* dst = (is_k ? kc : vc) + ((r * nkv + kvh) * S_max + p) * D + it.grp * 8;
     *reinterpret_cast<u16x8*>(dst) = b1;
     *reinterpret_cast<u16x8*>(dst + HALF) = b2;
   }
@@ -284,14 +261,8 @@ void check_cache(const at::Tensor& k_cache, const at::Tensor& v_cache, int64_t n
 }
 
 void check_qkv(const at::Tensor& qkv, int64_t nq, int64_t nkv, int64_t D, const char* name) {
-  DTG_CHECK_CUDA_BF16(qkv);
-  DTG_CHECK(D == 64 || D == 128, name, ": head_dim must be 64 or 128");
-  DTG_CHECK(nq >= 1 && nkv >= 1 && nq % nkv == 0 && nq + 2 * nkv < (1 << 20), name, ": bad head counts");
-  DTG_CHECK(qkv.dim() == 2 && qkv.stride(1) == 1 && qkv.stride(0) % 8 == 0 &&
-                reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
-            name, ": qkv must be [T, C] with 16-B aligned rows");
-  DTG_CHECK(qkv.size(1) >= (nq + 2 * nkv) * D, name, ": not enough columns for the q, k and v heads");
-  DTG_CHECK(qkv.size(0) == 0 || qkv.stride(0) >= qkv.size(1), name, ": overlapping rows");
+  DTG_CHECK(nq >= 1 && nkv >= 1 && nq % nkv == 0, name, ": bad head counts");
+  rope::check_qkv(qkv, nq + 2 * nkv, D, name);
 }
 
 void check_index(const at::Tensor& t, int64_t n, const char* name, const char* what) {
@@ -310,35 +281,19 @@ void kv_cache_append_(const at::Tensor& qkv, const at::Tensor& k_cache, const at
   check_cache(k_cache, v_cache, nkv, D, name);
   const int64_t T = qkv.size(0);
   check_index(rows, T, name, "rows");
-  DTG_CHECK(pos.is_cuda() && pos.scalar_type() == at::kLong && pos.is_contiguous() && pos.numel() == T, name,
-            ": position ids must be int64 [T]");
-  const bool rope = cos_t.numel() > 0;
-  if (rope) {
-    DTG_CHECK(cos_t.is_cuda() && sin_t.is_cuda() && cos_t.scalar_type() == at::kFloat &&
-                  sin_t.scalar_type() == at::kFloat && cos_t.dim() == 2 && cos_t.is_contiguous() &&
-                  sin_t.is_contiguous() && cos_t.size(1) == D / 2 && sin_t.sizes() == cos_t.sizes(),
-              name, ": tables must be contiguous f32 [max_pos, D/2]");
-  } else {
-    DTG_CHECK(sin_t.numel() == 0, name, ": cos and sin must both be empty for the copy-only form");
-  }
+  rope::check_pos(pos, T, name);
+  const bool rope = rope::enabled(cos_t, sin_t, name);  // empty tables: the copy-only form
+  const int64_t max_pos = rope ? rope::check_tables(cos_t, sin_t, D, name) : 0;
   if (T == 0) return;
   const c10::DeviceGuard g(qkv.device());
-  const int64_t total = T * (nq + 2 * nkv) * (D / 16);
-  const int64_t nblk = (total + 255) / 256;
+  const int64_t nblk = (rope::items(T, nq + 2 * nkv, D) + 255) / 256;
   DTG_CHECK(nblk < (int64_t(1) << 31), name, ": too many tokens");
   const float* cp = rope ? cos_t.data_ptr<float>() : nullptr;
   const float* sp = rope ? sin_t.data_ptr<float>() : nullptr;
-  const int64_t max_pos = rope ? cos_t.size(0) : 0;
-#define DTG_APPEND_LAUNCH(D_, R_)                                                                                  \
-  kv_append_kernel<D_, R_><<<(unsigned)nblk, 256, 0, stream()>>>(                                                  \
-      bf16_mut(qkv), qkv.stride(0), bf16_mut(k_cache), bf16_mut(v_cache), cp, sp, max_pos, pos.data_ptr<int64_t>(), \
-      rows.data_ptr<int32_t>(), (int)nq, (int)nkv, T, k_cache.size(0), k_cache.size(2))
-  if (D == 128) {
-    if (rope) DTG_APPEND_LAUNCH(128, true); else DTG_APPEND_LAUNCH(128, false);
-  } else {
-    if (rope) DTG_APPEND_LAUNCH(64, true); else DTG_APPEND_LAUNCH(64, false);
-  }
-#undef DTG_APPEND_LAUNCH
+  DTG_HD_RP_DISPATCH(D, rope, kv_append_kernel<HD, RP><<<(unsigned)nblk, 256, 0, stream()>>>(
+                                  bf16_mut(qkv), qkv.stride(0), bf16_mut(k_cache), bf16_mut(v_cache), cp, sp, max_pos,
+                                  pos.data_ptr<int64_t>(), rows.data_ptr<int32_t>(), (int)nq, (int)nkv, T,
+                                  k_cache.size(0), k_cache.size(2)));
   DTG_LAUNCH_CHECK();
 }
 
@@ -385,21 +340,13 @@ at::Tensor decode_attn(const at::Tensor& qkv, const at::Tensor& k_cache, const a
     case 8: DTG_DECODE_LAUNCH(D_, 8); break;              \
     default: DTG_DECODE_LAUNCH(D_, 16); break;            \
   }
-  if (D == 128) {
-    DTG_DECODE_G(128)
-  } else {
-    DTG_DECODE_G(64)
-  }
+  DTG_HD_DISPATCH(D, DTG_DECODE_G(HD))
 #undef DTG_DECODE_G
 #undef DTG_DECODE_LAUNCH
   DTG_LAUNCH_CHECK();
   if (p.splits > 1) {
-    if (D == 128)
-      decode_combine_kernel<128><<<(unsigned)(B * nkv), decode::kThreads, 0, stream()>>>(ws_o, ws_ml, bf16_mut(out),
-                                                                                         (int)G, p.splits);
-    else
-      decode_combine_kernel<64><<<(unsigned)(B * nkv), decode::kThreads, 0, stream()>>>(ws_o, ws_ml, bf16_mut(out),
-                                                                                        (int)G, p.splits);
+    DTG_HD_DISPATCH(D, decode_combine_kernel<HD><<<(unsigned)(B * nkv), decode::kThreads, 0, stream()>>>(
+                           ws_o, ws_ml, bf16_mut(out), (int)G, p.splits));
     DTG_LAUNCH_CHECK();
   }
   return out;

@@ -65,9 +65,7 @@ __global__ __launch_bounds__(256) void embedding_bwd_chunks_kernel(
       if (!before && !after) {
         add_row(out + id * out_stride, c, acc);
       } else {
-        float* slot = partial + ((chunk * 2 + (before ? 0 : 1)) * (int64_t)H + c);
-        *reinterpret_cast<float4*>(slot) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        *reinterpret_cast<float4*>(slot + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
+        store8f(partial + ((chunk * 2 + (before ? 0 : 1)) * (int64_t)H + c), acc);
       }
     }
     a = b;

@@ -26,8 +26,8 @@
 //    (the swizzle depends on the low 4 row bits only, so tile/step offsets are immediates).
 //  * Global -> register staging goes through buffer descriptors: rows past the end of a
 //    sequence read as zeros from the range check, with no per-row branches.
-#include "common.h"
 #include "flash_attn_plan.h"
+#include "rope_common.h"
 
 #include <ATen/hip/HIPGeneratorImpl.h>
 #include <ATen/hip/PhiloxUtils.cuh>
@@ -40,10 +40,6 @@
 #include <cmath>
 
 namespace dtg {
-
-// csrc/kernels/rope.hip
-void rope_rows_launch(uint16_t* x, int64_t row_stride, int nheads, int head_dim, const float* cos_t,
-                      const float* sin_t, const int64_t* pos, int64_t T, bool inverse, hipStream_t st);
 
 namespace fa {
 
@@ -558,8 +554,9 @@ struct BwdParams {
 // Inverse rotary rotation of a row-per-lane accumulator (lane = row, registers = columns
 // 32d + 8g + 4h + e) in place, in f32 before the single bf16 rounding of the store: the backward
 // of q' = q cos + rotate_half(q) sin, i.e. (x1, x2) -> (x1 cos + x2 sin, x2 cos - x1 sin) for the
-// column pairs (i, i + D/2), which live in tiles d and d + ND/2 of the same register.  Same
-// semantics as rope_kernel(inverse = true), one rounding fewer.
+// column pairs (i, i + D/2), which live in tiles d and d + ND/2 of the same register.  The pairing
+// and the sign convention are those of rope_common.h (rope::rotate_inv); the register layout is the
+// MFMA epilogue's, so the loop stays here.  One rounding fewer than rope_kernel(inverse = true).
 template <int ND>
 __device__ __forceinline__ void rope_inv_rows(f32x16* acc, const float* cos_t, const float* sin_t, int64_t p) {
   constexpr int HT = ND / 2;     // tiles in the first half
@@ -1381,16 +1378,10 @@ static void flash_attn_bwd_impl(const at::Tensor& dout_, const at::Tensor& q, co
                   (int)hkv, (float)scale, (float)(scale * fa::kLog2e), nullptr, nullptr, 0};
   const fa::Call c = checked_call(q, hkv, nseq, max_seqlen, causal, op, &P.kstart, &P.klen);
   P.window = fa::window_eff(c);
-  if (op.rope_cos != nullptr) {
-    const at::Tensor &ct = *op.rope_cos, &stb = *op.rope_sin, &pt = *op.rope_pos;
-    DTG_CHECK(ct.is_cuda() && ct.scalar_type() == at::kFloat && stb.scalar_type() == at::kFloat && ct.is_contiguous() &&
-                  stb.is_contiguous() && ct.dim() == 2 && ct.size(1) == D / 2 && stb.sizes() == ct.sizes(),
-              "flash_attn rope: tables must be contiguous f32 [max_pos, D/2] on the GPU");
-    DTG_CHECK(pt.is_cuda() && pt.scalar_type() == at::kLong && pt.is_contiguous() && pt.numel() == T,
-              "flash_attn rope: position ids must be int64 [T] on the GPU");
-    P.rope_cos = ct.data_ptr<float>();
-    P.rope_sin = stb.data_ptr<float>();
-    P.rope_pos = pt.data_ptr<int64_t>();
+  if (op.rope_cos != nullptr) {  // checked by flash_attn_bwd_fused
+    P.rope_cos = op.rope_cos->data_ptr<float>();
+    P.rope_sin = op.rope_sin->data_ptr<float>();
+    P.rope_pos = op.rope_pos->data_ptr<int64_t>();
   }
   if (const char* why = fa::conflict(c)) DTG_CHECK(false, why);
   if (op.drop != nullptr) P.drop = *op.drop;
@@ -1418,10 +1409,13 @@ static at::Tensor flash_attn_bwd_fused(const char* name, const at::Tensor& dout,
                                        int64_t nkv, int64_t D, const at::Tensor& o, const at::Tensor& lse,
                                        const at::Tensor& cu_seqlens, int64_t max_seqlen, double scale, bool causal,
                                        const AttnOpts& op) {
-  DTG_CHECK_CUDA_BF16(qkv);
+  rope::check_qkv(qkv, nq + 2 * nkv, D, name);
   const int64_t T = qkv.size(0);
-  DTG_CHECK(qkv.dim() == 2 && qkv.size(1) == (nq + 2 * nkv) * D && qkv.stride(1) == 1, name,
-            ": qkv must be [T, (nq + 2 nkv) * D]");
+  DTG_CHECK(qkv.size(1) == (nq + 2 * nkv) * D, name, ": qkv must be [T, (nq + 2 nkv) * D]");
+  if (op.rope_cos != nullptr) {
+    rope::check_tables(*op.rope_cos, *op.rope_sin, D, name);
+    rope::check_pos(*op.rope_pos, T, name);
+  }
   auto dqkv = at::empty({T, (nq + 2 * nkv) * D}, qkv.options());
   auto view3 = [&](const at::Tensor& t, int64_t h0, int64_t nh) {
     return t.as_strided({T, nh, D}, {t.stride(0), D, 1}, t.storage_offset() + h0 * D);

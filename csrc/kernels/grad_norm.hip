@@ -21,24 +21,6 @@ constexpr int kSqThreads = 256;
 constexpr int kSqVec = 8;          // elements per lane per vector: 16 B of bf16, 32 B of f32
 constexpr int kSqMaxBlocks = 2048;  // 8 workgroups of 256 per CU on 256 CUs: every wave slot filled
 
-template <typename T>
-__device__ __forceinline__ float sq_ld(const T* p, int64_t i);
-template <>
-__device__ __forceinline__ float sq_ld<uint16_t>(const uint16_t* p, int64_t i) { return bf2f(p[i]); }
-template <>
-__device__ __forceinline__ float sq_ld<float>(const float* p, int64_t i) { return p[i]; }
-
-template <typename T>
-__device__ __forceinline__ void sq_ld8(const T* p, float* o);
-template <>
-__device__ __forceinline__ void sq_ld8<uint16_t>(const uint16_t* p, float* o) { load8(p, o); }
-template <>
-__device__ __forceinline__ void sq_ld8<float>(const float* p, float* o) {
-  const f32x4 a = reinterpret_cast<const f32x4*>(p)[0], b = reinterpret_cast<const f32x4*>(p)[1];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { o[j] = a[j]; o[4 + j] = b[j]; }
-}
-
 // g: `head` scalar elements, then `nbody` (a multiple of 8) elements from a 16-byte boundary,
 // then `tail` scalar elements; head, tail < 8.
 template <typename T, int U>
@@ -54,7 +36,7 @@ __global__ __launch_bounds__(kSqThreads) void sumsq_partial_kernel(const T* __re
   for (; i + (U - 1) * stride < nbody; i += U * stride) {
     float x[U][kSqVec];
 #pragma unroll
-    for (int u = 0; u < U; ++u) sq_ld8<T>(body + i + u * stride, x[u]);
+    for (int u = 0; u < U; ++u) ld8(body + i + u * stride, x[u]);
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -62,17 +44,17 @@ __global__ __launch_bounds__(kSqThreads) void sumsq_partial_kernel(const T* __re
   }
   for (; i < nbody; i += stride) {
     float x[kSqVec];
-    sq_ld8<T>(body + i, x);
+    ld8(body + i, x);
 #pragma unroll
     for (int j = 0; j < kSqVec; ++j) s[0] += x[j] * x[j];
   }
   if (blockIdx.x == 0) {
     const int t = threadIdx.x;
     if (t < head) {
-      const float x = sq_ld<T>(g, t);
+      const float x = ld(g, t);
       s[0] += x * x;
     } else if (t >= kWave && t - kWave < tail) {
-      const float x = sq_ld<T>(body, nbody + (t - kWave));
+      const float x = ld(body, nbody + (t - kWave));
       s[0] += x * x;
     }
   }

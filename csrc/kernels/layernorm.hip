@@ -207,8 +207,8 @@ __global__ __launch_bounds__(kThreads) void layernorm_bwd_kernel(
   for (int i = 0; i < PER; ++i) {
     const int c = threadIdx.x + i * kThreads;
     if (c < nch) {
-      norm::store8f(dw_part + (int64_t)blockIdx.x * H + c * 8, dwacc[i]);
-      norm::store8f(db_part + (int64_t)blockIdx.x * H + c * 8, dbacc[i]);
+      store8f(dw_part + (int64_t)blockIdx.x * H + c * 8, dwacc[i]);
+      store8f(db_part + (int64_t)blockIdx.x * H + c * 8, dbacc[i]);
     }
   }
 }

@@ -11,13 +11,6 @@
 namespace dtg {
 namespace norm {
 
-// Stores 8 f32 accumulators (a lane's partial sums for one 16-byte chunk of bf16 columns).
-__device__ __forceinline__ void store8f(float* p, const float* v) {
-  float4* dst = reinterpret_cast<float4*>(p);
-  dst[0] = make_float4(v[0], v[1], v[2], v[3]);
-  dst[1] = make_float4(v[4], v[5], v[6], v[7]);
-}
-
 // Column sums of the [gridDim.y, nrows, W] f32 partials -> bf16 [gridDim.y, W], fixed summation
 // order (deterministic).  16 columns x 16 row groups per workgroup: W / 16 workgroups (256 at
 // W = 4096, one per CU) each walking nrows / 16 rows -- the 32-column form had half the chip idle

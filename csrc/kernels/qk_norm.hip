@@ -3,7 +3,7 @@
 //
 // Forward, per (token, head < nq + nkv):  y = w * x * rsqrt(mean(x^2) + eps)  in f32 (w = the q weight
 // for heads below nq, the k weight otherwise; both [D], shared by all heads), then the rotation of
-// rope.hip (pairs (i, i + D/2), f32 tables [max_pos, D/2], int64 pos[T]), one bf16 rounding on the
+// rope_common.h (pairs (i, i + D/2), f32 tables [max_pos, D/2], int64 pos[T]), one bf16 rounding on the
 // store.  The same pass copies the pre-norm q|k bits to a contiguous xqk [T, (nq + nkv) * D]: the
 // backward needs x, and x cannot be recovered from y (weights may be zero).
 //
@@ -20,26 +20,9 @@
 // mean is a 3- or 2-step sub-wave butterfly.  A wave therefore carries 8 (16) heads.  ROPE = false
 // is the norm-only form (empty tables), used before the Ulysses all-to-all.
 #include "norm_common.h"
+#include "rope_common.h"
 
 namespace dtg {
-
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
-__device__ __forceinline__ void load8f(const float* p, float* out) {
-  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-  out[0] = a.x; out[1] = a.y; out[2] = a.z; out[3] = a.w;
-  out[4] = b.x; out[5] = b.y; out[6] = b.z; out[7] = b.w;
-}
-
-__device__ __forceinline__ void widen8(const u16x8& v, float* out) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) out[i] = bf2f(v[i]);
-}
 
 // One lane group per (token, head); every lane reaches the butterfly (lanes past the end carry zeros).
 template <int D, bool ROPE>
@@ -49,20 +32,17 @@ __global__ __launch_bounds__(norm::kThreads) void qk_norm_rope_fwd_kernel(
     const int64_t* __restrict__ pos, uint16_t* __restrict__ xqk, float* __restrict__ rstd_out, int nq, int nh,
     int64_t T, float eps) {
   constexpr int HALF = D / 2;
-  constexpr int GROUPS = HALF / 8;
   const int64_t gid = (int64_t)blockIdx.x * norm::kThreads + threadIdx.x;
-  const bool valid = gid < T * nh * GROUPS;
-  const int grp = gid % GROUPS;
-  const int64_t th = gid / GROUPS;
-  const int head = th % nh;
-  const int64_t tok = th / nh;
+  const bool valid = gid < rope::items(T, nh, D);
+  const rope::Item<D> it(gid, nh);
+  const int grp = it.grp;
   uint16_t* base = nullptr;
   u16x8 r1{0, 0, 0, 0, 0, 0, 0, 0}, r2{0, 0, 0, 0, 0, 0, 0, 0};
   if (valid) {
-    base = qkv + tok * row_stride + (int64_t)head * D + grp * 8;
+    base = it.in(qkv, row_stride);
     r1 = *reinterpret_cast<const u16x8*>(base);
     r2 = *reinterpret_cast<const u16x8*>(base + HALF);
-    uint16_t* xo = xqk + th * D + grp * 8;
+    uint16_t* xo = xqk + it.th * D + grp * 8;
     *reinterpret_cast<u16x8*>(xo) = r1;
     *reinterpret_cast<u16x8*>(xo + HALF) = r2;
   }
@@ -72,11 +52,11 @@ __global__ __launch_bounds__(norm::kThreads) void qk_norm_rope_fwd_kernel(
   float ss = 0.f;
 #pragma unroll
   for (int j = 0; j < 8; ++j) ss += x1[j] * x1[j] + x2[j] * x2[j];
-  ss = group_sum<GROUPS>(ss);
+  ss = lanes_sum<rope::Item<D>::GROUPS>(ss);
   if (!valid) return;
   const float rstd = rsqrtf(ss * (1.0f / D) + eps);
-  if (grp == 0) rstd_out[th] = rstd;
-  const uint16_t* w = (head < nq ? wq : wk) + grp * 8;
+  if (grp == 0) rstd_out[it.th] = rstd;
+  const uint16_t* w = (it.head < nq ? wq : wk) + grp * 8;
   float w1[8], w2[8], y1[8], y2[8];
   load8(w, w1);
   load8(w + HALF, w2);
@@ -86,21 +66,12 @@ __global__ __launch_bounds__(norm::kThreads) void qk_norm_rope_fwd_kernel(
     y2[j] = w2[j] * (x2[j] * rstd);
   }
   if constexpr (ROPE) {
-    const int64_t p = pos[tok];
-    float c[8], s[8], o1[8], o2[8];
-    load8f(cos_t + p * HALF + grp * 8, c);
-    load8f(sin_t + p * HALF + grp * 8, s);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      o1[j] = y1[j] * c[j] - y2[j] * s[j];
-      o2[j] = y2[j] * c[j] + y1[j] * s[j];
-    }
-    store8(base, o1);
-    store8(base + HALF, o2);
-  } else {
-    store8(base, y1);
-    store8(base + HALF, y2);
+    float c[8], s[8];
+    rope::load_cs<D>(cos_t, sin_t, pos[it.tok], grp, c, s);
+    rope::rotate(y1, y2, c, s, y1, y2);
   }
+  store8(base, y1);
+  store8(base + HALF, y2);
 }
 
 // A workgroup owns `tok_per_block` tokens; its 256 / GROUPS lane groups walk their (token, head) items
@@ -153,17 +124,9 @@ __global__ __launch_bounds__(norm::kThreads) void qk_norm_rope_bwd_kernel(
     widen8(r2, x2);
     if constexpr (ROPE) {
       if (valid) {  // dy = R(-theta) g
-        const int64_t p = pos[tok];
         float c[8], s[8];
-        load8f(cos_t + p * HALF + grp * 8, c);
-        load8f(sin_t + p * HALF + grp * 8, s);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float a = d1[j] * c[j] + d2[j] * s[j];
-          const float b = d2[j] * c[j] - d1[j] * s[j];
-          d1[j] = a;
-          d2[j] = b;
-        }
+        rope::load_cs<D>(cos_t, sin_t, pos[tok], grp, c, s);
+        rope::rotate_inv(d1, d2, c, s, d1, d2);
       }
     }
     float dot = 0.f;
@@ -183,7 +146,7 @@ __global__ __launch_bounds__(norm::kThreads) void qk_norm_rope_bwd_kernel(
       d2[j] *= w2[j];
       dot += d1[j] * x1[j] + d2[j] * x2[j];
     }
-    dot = group_sum<GROUPS>(dot) * (1.0f / D);
+    dot = lanes_sum<GROUPS>(dot) * (1.0f / D);
     if (valid) {
       float o1[8], o2[8];
 #pragma unroll
@@ -215,41 +178,19 @@ __global__ __launch_bounds__(norm::kThreads) void qk_norm_rope_bwd_kernel(
 static bool qk_check(const at::Tensor& qkv, const at::Tensor& wq, const at::Tensor& wk, const at::Tensor& cos_t,
                      const at::Tensor& sin_t, const at::Tensor& pos, int64_t nq, int64_t nkv, int64_t D,
                      const char* name) {
-  DTG_CHECK_CUDA_BF16(qkv);
+  DTG_CHECK(nq >= 1 && nkv >= 1, name, ": bad head counts");
+  rope::check_qkv(qkv, nq + nkv, D, name);
   DTG_CHECK_CUDA_BF16(wq);
   DTG_CHECK_CUDA_BF16(wk);
-  DTG_CHECK(D == 64 || D == 128, name, ": head_dim must be 64 or 128");
-  DTG_CHECK(nq >= 1 && nkv >= 1 && nq + nkv < (1 << 20), name, ": bad head counts");
-  DTG_CHECK(qkv.dim() == 2 && qkv.stride(1) == 1 && qkv.stride(0) % 8 == 0 &&
-                reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
-            name, ": qkv must be [T, C] with 16-B aligned rows");
-  DTG_CHECK(qkv.size(1) >= (nq + nkv) * D, name, ": not enough columns for the q and k heads");
-  DTG_CHECK(qkv.size(0) == 0 || qkv.stride(0) >= qkv.size(1), name, ": overlapping rows");
   DTG_CHECK(wq.numel() == D && wk.numel() == D && wq.is_contiguous() && wk.is_contiguous(), name,
             ": weights must be contiguous [head_dim]");
-  const bool rope = cos_t.numel() > 0;
+  const bool rope = rope::enabled(cos_t, sin_t, name);  // empty tables: the norm-only form
   if (rope) {
-    DTG_CHECK(cos_t.is_cuda() && sin_t.is_cuda() && pos.is_cuda(), name, ": tables and positions must be GPU tensors");
-    DTG_CHECK(cos_t.scalar_type() == at::kFloat && sin_t.scalar_type() == at::kFloat && cos_t.dim() == 2 &&
-                  cos_t.is_contiguous() && sin_t.is_contiguous() && cos_t.size(1) == D / 2 &&
-                  sin_t.sizes() == cos_t.sizes(),
-              name, ": tables must be contiguous f32 [max_pos, D/2]");
-    DTG_CHECK(pos.scalar_type() == at::kLong && pos.is_contiguous() && pos.numel() == qkv.size(0), name,
-              ": position ids must be int64 [T]");
-  } else {
-    DTG_CHECK(sin_t.numel() == 0, name, ": cos and sin must both be empty for the norm-only form");
+    rope::check_tables(cos_t, sin_t, D, name);
+    rope::check_pos(pos, qkv.size(0), name);
   }
   return rope;
 }
-
-#define DTG_QK_DISPATCH(D_, rope, ...)                                           \
-  if (D_ == 128) {                                                               \
-    if (rope) { constexpr int HD = 128; constexpr bool RP = true; __VA_ARGS__; }  \
-    else { constexpr int HD = 128; constexpr bool RP = false; __VA_ARGS__; }      \
-  } else {                                                                       \
-    if (rope) { constexpr int HD = 64; constexpr bool RP = true; __VA_ARGS__; }   \
-    else { constexpr int HD = 64; constexpr bool RP = false; __VA_ARGS__; }       \
-  }
 
 std::tuple<at::Tensor, at::Tensor> qk_norm_rope_fwd_(const at::Tensor& qkv, const at::Tensor& wq,
                                                      const at::Tensor& wk, const at::Tensor& cos_t,
@@ -261,13 +202,12 @@ std::tuple<at::Tensor, at::Tensor> qk_norm_rope_fwd_(const at::Tensor& qkv, cons
   auto xqk = at::empty({T, nh * head_dim}, qkv.options());
   auto rstd = at::empty({T, nh}, qkv.options().dtype(at::kFloat));
   if (T == 0) return {xqk, rstd};
-  const int64_t total = T * nh * (head_dim / 16);
-  const int64_t nblk = (total + norm::kThreads - 1) / norm::kThreads;
+  const int64_t nblk = (rope::items(T, nh, head_dim) + norm::kThreads - 1) / norm::kThreads;
   DTG_CHECK(nblk < (int64_t(1) << 31), "qk_norm_rope_fwd_: too many tokens");
   const float* cp = rope ? cos_t.data_ptr<float>() : nullptr;
   const float* sp = rope ? sin_t.data_ptr<float>() : nullptr;
   const int64_t* pp = rope ? pos.data_ptr<int64_t>() : nullptr;
-  DTG_QK_DISPATCH(head_dim, rope,
+  DTG_HD_RP_DISPATCH(head_dim, rope,
                   qk_norm_rope_fwd_kernel<HD, RP><<<(unsigned)nblk, norm::kThreads, 0, stream()>>>(
                       bf16_mut(qkv), qkv.stride(0), bf16_ptr(wq), bf16_ptr(wk), cp, sp, pp, bf16_mut(xqk),
                       rstd.data_ptr<float>(), (int)nq, (int)nh, T, (float)eps));
@@ -299,7 +239,7 @@ std::tuple<at::Tensor, at::Tensor> qk_norm_rope_bwd_(const at::Tensor& dqkv, con
   const float* cp = rope ? cos_t.data_ptr<float>() : nullptr;
   const float* sp = rope ? sin_t.data_ptr<float>() : nullptr;
   const int64_t* pp = rope ? pos.data_ptr<int64_t>() : nullptr;
-  DTG_QK_DISPATCH(head_dim, rope,
+  DTG_HD_RP_DISPATCH(head_dim, rope,
                   qk_norm_rope_bwd_kernel<HD, RP><<<(unsigned)nb, norm::kThreads, 0, stream()>>>(
                       bf16_mut(dqkv), dqkv.stride(0), bf16_ptr(xqk), rstd.data_ptr<float>(), bf16_ptr(wq),
                       bf16_ptr(wk), cp, sp, pp, part.data_ptr<float>(), (int)nq, (int)nh, T, (int)tpb));

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(norm::kThreads) void rmsnorm_bwd_kernel(
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int c = threadIdx.x + i * norm::kThreads;
-    if (c < nch) norm::store8f(dw_part + (int64_t)blockIdx.x * H + c * 8, dwacc[i]);
+    if (c < nch) store8f(dw_part + (int64_t)blockIdx.x * H + c * 8, dwacc[i]);
   }
 }
 

@@ -201,6 +201,32 @@ def check_rope(dev, D, T, nh):
         fz = full.to(dev, copy=True)
         dops.rope_(fz[:, lo:lo + C], cd, sd, torch.zeros(T, dtype=torch.int64, device=dev), nh, D, inverse)
         assert torch.equal(_cpu(fz), full), "position 0 must leave the buffer as it is"
+    _check_rope_last_row(dev, D)
+
+
+def _check_rope_last_row(dev, D):
+    """Three tokens at positions {0, 1, max_pos - 1}, 3 rotated heads in a buffer of 4 heads whose row
+    stride is wider than its columns: pins the (token, head, group) decode at a head count that is not
+    the buffer's and the table load at the last row.  Forward then inverse: head 4 and the padding keep
+    their bits, the rotated heads return within the round-trip bound."""
+    T, nh, lo = 3, 3, 8
+    C = 4 * D
+    full = torch.randn(T, lo + C + 24, generator=_gen(7 * D)).to(BF)
+    cos, sin = rope_tables(D)
+    pos = torch.tensor([0, 1, ROPE_MAX_POS - 1])
+    fd = full.to(dev, copy=True)
+    view = fd[:, lo:lo + C]
+    assert view.stride(0) > view.size(1)
+    for inverse in (False, True):
+        dops.rope_(view, cos.to(dev), sin.to(dev), pos.to(dev), nh, D, inverse)
+        out = _cpu(fd)
+        keep = torch.ones(full.shape[1], dtype=torch.bool)
+        keep[lo:lo + nh * D] = False
+        assert torch.equal(out[:, keep], full[:, keep]), "rope wrote to head 4 or to the padding columns"
+        if not inverse:
+            assert not torch.equal(out[2, ~keep], full[2, ~keep]), "the token on the last table row was not rotated"
+    rt = R.rope_roundtrip_term(full[:, lo:lo + C], cos, sin, pos, nh, D)
+    R.assert_within(out[:, lo:lo + nh * D], R.f64(full[:, lo:lo + nh * D]), rt[:, :nh * D], "rope_ last row round trip")
 
 
 def check_rope_empty(dev):
