@@ -18,4 +18,8 @@ def __getattr__(name):  # `from dtg import generate` without importing torch at 
         from .models.decode_graph import GraphedDecode
 
         return GraphedDecode
+    if name == "Fp8DecodeWeights":
+        from .models.quantized import Fp8DecodeWeights
+
+        return Fp8DecodeWeights
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

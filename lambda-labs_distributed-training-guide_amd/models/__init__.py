@@ -5,6 +5,7 @@ from .config import GPT2Config, LlamaConfig, available_configs, resolve_config
 from .decode_graph import GraphedDecode
 from .generation import KVCache, decode_bucket, decode_step, generate, prefill
 from .gpt2 import GPT2LMHeadModel
+from .quantized import Fp8DecodeWeights
 from .llama import CausalLMOutput, LlamaForCausalLM, count_valid_labels
 
 
@@ -62,4 +63,4 @@ def resize_token_embeddings(model, new_vocab: int):
 __all__ = ["GPT2Config", "LlamaConfig", "available_configs", "resolve_config", "GPT2LMHeadModel",
            "LlamaForCausalLM", "CausalLMOutput", "count_valid_labels", "build_model", "resize_token_embeddings",
            "mean_resized_rows", "KVCache", "prefill", "decode_step", "generate", "decode_bucket",
-           "GraphedDecode"]
+           "GraphedDecode", "Fp8DecodeWeights"]

@@ -20,7 +20,8 @@ What makes the step replayable:
 The first `warmup` steps of a run that has no graph for its bucket yet are real eager steps on the
 capture stream (lazy initialisation, allocator warm-up); the capture itself executes nothing, so the
 cache is not advanced by it.  All work runs on one dedicated stream: the graph is a plain chain of
-kernels.  With linear="skinny" every kernel of the step is this project's and deterministic, and the
+kernels.  With linear="skinny" (and "skinny-fp8", whose e4m3 weight copies are static device tensors
+held by this object) every kernel of the step is this project's and deterministic, and the
 captured loop returns the ids of `generate(..., decode="eager", bucketed=True)` bit for bit; with
 linear="blas" hipBLASLt may choose other algorithms under capture and the two agree to rounding.
 """
@@ -40,13 +41,14 @@ _NO_EOS = -(2 ** 62)  # no id equals it
 class GraphedDecode:
     """The captured decode loop of `model` for `n` sequences and a cache of `s_max` positions."""
 
-    def __init__(self, model, n: int, s_max: int, linear: str = "skinny", warmup: int = 2):
+    def __init__(self, model, n: int, s_max: int, linear: str = "skinny", warmup: int = 2, fp8=None):
         _g._check_model(model)
         _g._check_linear(linear, n)
         dev = model.embed_tokens.weight.device
         if dev.type != "cuda":
             raise ValueError("GraphedDecode needs a GPU (HIP-graph capture)")
         self.model, self.n, self.s_max, self.linear, self.warmup = model, int(n), int(s_max), linear, int(warmup)
+        self.fp8 = _g._check_fp8(model, linear, fp8, build=True)  # linear="skinny-fp8": static device tensors
         self.cache = _g.KVCache(model.config, self.n, self.s_max, device=dev, dtype=model.embed_tokens.weight.dtype)
         i64 = dict(dtype=torch.long, device=dev)
         self.rows = torch.arange(self.n, dtype=torch.int32, device=dev)
@@ -83,7 +85,7 @@ class GraphedDecode:
         self.done |= nxt == self.eos
 
     def _step(self, plan_len: int, fused: bool):
-        self._choose(_g._decode_body(self.model, self.tok, self.cache, self.rows, plan_len, self.linear), fused)
+        self._choose(_g._decode_body(self.model, self.tok, self.cache, self.rows, plan_len, self.linear, self.fp8), fused)
 
     def _capture(self, bucket: int, fused: bool) -> torch.cuda.CUDAGraph:
         """Record one step planned for `bucket` (nothing executes; the first replay performs it)."""
@@ -128,7 +130,7 @@ class GraphedDecode:
                 for k, v in fused.items():
                     self.params[k].copy_(torch.tensor(v, dtype=self.params[k].dtype), non_blocking=False)
                 self.seed.fill_((int(seed) + 2 ** 63) % 2 ** 64 - 2 ** 63)
-            self._choose(_g.prefill(self.model, prompts, cache), use_fused)
+            self._choose(_g.prefill(self.model, prompts, cache, fp8=self.fp8), use_fused)
             run_eager = 0  # eager steps of this run: the warm-up before its first capture
             for step in range(1, max_new_tokens):
                 if eos_token_id is not None and step % _g.HOST_CHECK_EVERY == 0 and bool(self.done.all()):

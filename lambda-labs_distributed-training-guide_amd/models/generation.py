@@ -58,23 +58,44 @@ class KVCache:
         self.max_len = 0
 
 
-LINEAR_MODES = ("blas", "skinny")
+LINEAR_MODES = ("blas", "skinny", "skinny-fp8")
 SKINNY_MAX_ROWS = 16  # = ops.functional.SKINNY_MAX_M: # sequences a decode step with linear="skinny" takes
 
 
 def _check_linear(linear, n=None):
     if linear not in LINEAR_MODES:
         raise ValueError(f"linear must be one of {LINEAR_MODES}, got {linear!r}")
-    if linear == "skinny" and n is not None and n > SKINNY_MAX_ROWS:
-        raise ValueError(f'linear="skinny" decodes at most {SKINNY_MAX_ROWS} sequences per step, got {n}')
+    if linear != "blas" and n is not None and n > SKINNY_MAX_ROWS:
+        raise ValueError(f'linear="{linear}" decodes at most {SKINNY_MAX_ROWS} sequences per step, got {n}')
 
 
-def _run_layers(model, x, append_and_attend, linear="blas"):
+def _check_fp8(model, linear, fp8, build=False):
+    """The FP8 weight copies of a linear="skinny-fp8" call: `fp8` as given, built when `build` allows it."""
+    if linear != "skinny-fp8":
+        if fp8 is not None:
+            raise ValueError(f'fp8 weights were given with linear={linear!r}; they need linear="skinny-fp8"')
+        return None
+    if fp8 is None:
+        if not build:
+            raise ValueError('linear="skinny-fp8" needs fp8=Fp8DecodeWeights(model)')
+        from .quantized import Fp8DecodeWeights
+
+        return Fp8DecodeWeights(model)
+    fp8.check(model)
+    return fp8
+
+
+def _run_layers(model, x, append_and_attend, linear="blas", fp8=None):
     """The decoder stack around a caller-supplied attention (qkv -> attention output).  linear="skinny"
     (a decode step of at most 16 rows): the qkv, o, gate_up (+ SwiGLU) and down projections run in
-    ops.skinny_linear instead of hipBLASLt."""
+    ops.skinny_linear instead of hipBLASLt; linear="skinny-fp8": in ops.skinny_linear_fp8 on the e4m3
+    copies `fp8` (models/quantized.py).  linear="blas" with `fp8` is the prefill of an FP8 run: hipBLASLt on
+    the bf16 matrices the copies stand for (`fp8.dequantized`, made one at a time and dropped), so the keys and
+    values the prompt leaves in the cache belong to the same quantised model as the decode steps that read them."""
     if linear == "skinny":
         return _run_layers_skinny(model, x, append_and_attend)
+    if linear == "skinny-fp8":
+        return _run_layers_skinny_fp8(model, x, append_and_attend, fp8)
     res = None
     for i, layer in enumerate(model.layers):
         if res is None:
@@ -83,10 +104,17 @@ def _run_layers(model, x, append_and_attend, linear="blas"):
             n, res = ops.add_rms_norm(x, res, layer.input_layernorm.weight, layer.eps)
         attn = layer.self_attn
         b = getattr(attn.qkv_proj, "bias", None)
-        qkv = ops.linear(n, attn.qkv_proj.weight, None if b is None else b.view(-1))
-        a = ops.linear(append_and_attend(i, attn, qkv), attn.o_proj.weight)
+        if fp8 is None:
+            w_qkv, w_o = attn.qkv_proj.weight, attn.o_proj.weight
+        else:
+            w_qkv, w_o = fp8.dequantized(f"layers.{i}.self_attn.qkv_proj"), fp8.dequantized(f"layers.{i}.self_attn.o_proj")
+        qkv = ops.linear(n, w_qkv, None if b is None else b.view(-1))
+        a = ops.linear(append_and_attend(i, attn, qkv), w_o)
         n2, res = ops.add_rms_norm(a, res, layer.post_attention_layernorm.weight, layer.eps)
-        x = layer.mlp(n2)
+        if fp8 is None:
+            x = layer.mlp(n2)
+        else:
+            x = ops.swiglu_mlp(n2, fp8.dequantized(f"layers.{i}.mlp.gate_up_proj"), fp8.dequantized(f"layers.{i}.mlp.down_proj"))
     return x, res
 
 
@@ -105,6 +133,22 @@ def _run_layers_skinny(model, x, append_and_attend):
     return x, res
 
 
+def _run_layers_skinny_fp8(model, x, append_and_attend, fp8):
+    res = None
+    for i, layer in enumerate(model.layers):
+        if res is None:
+            n, res = ops.rms_norm(x, layer.input_layernorm.weight, layer.eps), x
+        else:
+            n, res = ops.add_rms_norm(x, res, layer.input_layernorm.weight, layer.eps)
+        attn = layer.self_attn
+        qkv = ops.skinny_linear_fp8(n, *fp8.layer(i, "self_attn.qkv_proj"), getattr(attn.qkv_proj, "bias", None))
+        a = ops.skinny_linear_fp8(append_and_attend(i, attn, qkv), *fp8.layer(i, "self_attn.o_proj"))
+        n2, res = ops.add_rms_norm(a, res, layer.post_attention_layernorm.weight, layer.eps)
+        h = ops.skinny_linear_fp8(n2, *fp8.layer(i, "mlp.gate_up_proj"), act="swiglu")
+        x = ops.skinny_linear_fp8(h, *fp8.layer(i, "mlp.down_proj"))
+    return x, res
+
+
 def _append(attn, qkv, cache, i, cos, sin, pos, rows, pos_max):
     """RoPE (after the per-head norm for Qwen3, whose fused pass ropes itself) and the cache write.
     `pos_max`: the host's largest position of the call, checked by the op (rows were checked by _rows)."""
@@ -116,11 +160,13 @@ def _append(attn, qkv, cache, i, cos, sin, pos, rows, pos_max):
                                pos_max=pos_max)
 
 
-def _last_logits(model, x, res, linear="blas"):
+def _last_logits(model, x, res, linear="blas", fp8=None):
     h, _ = ops.add_rms_norm(x, res, model.norm.weight, model.config.rms_norm_eps)
-    if linear == "skinny":
+    if linear == "skinny-fp8" and fp8.has_head:
+        return ops.skinny_linear_fp8(h, *fp8.head())
+    if linear in ("skinny", "skinny-fp8"):
         return ops.skinny_linear(h, model.lm_head_weight())
-    return ops.linear(h, model.lm_head_weight())
+    return ops.linear(h, fp8.dequantized("lm_head") if fp8 is not None and fp8.has_head else model.lm_head_weight())
 
 
 def _rows(cache, n, rows, device):
@@ -134,10 +180,16 @@ def _rows(cache, n, rows, device):
 
 
 @torch.no_grad()
-def prefill(model, prompts: Sequence[torch.Tensor], cache: KVCache, rows: Optional[Sequence[int]] = None):
+def prefill(model, prompts: Sequence[torch.Tensor], cache: KVCache, rows: Optional[Sequence[int]] = None, fp8=None):
     """Run the prompts (1-D id tensors of any lengths >= 1) packed token-major, fill cache rows `rows`
-    (default 0..n-1) from position 0 and return the logits [n, V] of each prompt's last token."""
+    (default 0..n-1) from position 0 and return the logits [n, V] of each prompt's last token.
+
+    `fp8` (an `Fp8DecodeWeights` of this model): the prefill of a linear="skinny-fp8" run.  The GEMMs stay
+    hipBLASLt in bf16, on the matrices the e4m3 copies stand for instead of the model's own, so prompt and
+    decode steps see one and the same (quantised) model."""
     _check_model(model)
+    if fp8 is not None:
+        fp8.check(model)
     lens = [int(p.numel()) for p in prompts]
     if not lens or min(lens) < 1:
         raise ValueError("prefill: every prompt needs at least one token")
@@ -157,14 +209,14 @@ def prefill(model, prompts: Sequence[torch.Tensor], cache: KVCache, rows: Option
         qkv = _append(attn, qkv, cache, i, cos, sin, pos, tok_rows, max_seqlen - 1)
         return ops.attention(qkv, attn.nq, attn.nkv, attn.d, cu, max_seqlen, window=attn.window)  # q, k roped already
 
-    x, res = _run_layers(model, ops.embedding(ids, model.embed_tokens.weight), attend)
+    x, res = _run_layers(model, ops.embedding(ids, model.embed_tokens.weight), attend, "blas", fp8)
     last = (cu[1:] - 1).long()
     cache.lens[rows_t.long()] = lens_t
     cache.max_len = max(cache.max_len, max_seqlen)
-    return _last_logits(model, x[last], res[last])
+    return _last_logits(model, x[last], res[last], "blas", fp8)
 
 
-def _decode_body(model, tokens, cache, rows_t, plan_len, linear):
+def _decode_body(model, tokens, cache, rows_t, plan_len, linear, fp8=None):
     """One decode step on device tensors only (`tokens` [n] ids, `rows_t` [n] int32 cache rows): nothing is
     built from host data and nothing is read back, so a HIP graph can record it.  `plan_len` is the host
     length of the attention's launch plan and of the append's position check.  Advances cache.lens, not the
@@ -179,19 +231,20 @@ def _decode_body(model, tokens, cache, rows_t, plan_len, linear):
         return ops.decode_attention(qkv, cache.k[i], cache.v[i], rows_t, new_lens, attn.nq, attn.nkv, attn.d, plan_len,
                                     window=attn.window)
 
-    x, res = _run_layers(model, ops.embedding(tokens, model.embed_tokens.weight), attend, linear)
+    x, res = _run_layers(model, ops.embedding(tokens, model.embed_tokens.weight), attend, linear, fp8)
     cache.lens[rows_t.long()] = new_lens
-    return _last_logits(model, x, res, linear)
+    return _last_logits(model, x, res, linear, fp8)
 
 
 @torch.no_grad()
 def decode_step(model, tokens: torch.Tensor, cache: KVCache, rows: Optional[Sequence[int]] = None,
-                linear: str = "blas", plan_len: Optional[int] = None):
+                linear: str = "blas", plan_len: Optional[int] = None, fp8=None):
     """One new token per active sequence (`tokens` [n], for cache rows `rows`, default 0..n-1): appends
     it at the row's current length and returns the next-token logits [n, V].
 
     linear="skinny": the five projections of the step (qkv, o, gate_up with its SwiGLU, down, LM head)
-    run in `ops.skinny_linear` (at most 16 sequences).  `plan_len`: the host length the attention's
+    run in `ops.skinny_linear` (at most 16 sequences); linear="skinny-fp8": in `ops.skinny_linear_fp8` on
+    the e4m3 weight copies `fp8` (an `Fp8DecodeWeights` of this model, required).  `plan_len`: the host length the attention's
     launch plan is made for, cache.max_len + 1 <= plan_len <= S_max (default cache.max_len + 1, the
     tightest); a captured step is planned for its whole length bucket, and an eager step given the same
     `plan_len` runs the same launches."""
@@ -201,13 +254,14 @@ def decode_step(model, tokens: torch.Tensor, cache: KVCache, rows: Optional[Sequ
     dev = cache.lens.device
     tokens = tokens.reshape(-1).to(dev)
     _check_linear(linear, tokens.numel())
+    fp8 = _check_fp8(model, linear, fp8)
     max_len = cache.max_len + 1
     if plan_len is None:
         plan_len = max_len
     if not max_len <= int(plan_len) <= cache.s_max:
         raise ValueError(f"decode_step: plan_len {plan_len} outside [cache.max_len + 1 = {max_len}, S_max = {cache.s_max}]")
     rows_t = _rows(cache, tokens.numel(), rows, dev)
-    logits = _decode_body(model, tokens, cache, rows_t, int(plan_len), linear)
+    logits = _decode_body(model, tokens, cache, rows_t, int(plan_len), linear, fp8)
     cache.max_len = max_len
     return logits
 
@@ -258,7 +312,7 @@ def _fused_params(n, **given):
 def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              top_p: float = 1.0, eos_token_id: Optional[int] = None, seed: int = 0, s_max: Optional[int] = None,
              min_p: float = 0.0, sampler: str = "torch", linear: str = "blas", decode="eager",
-             bucketed: bool = False) -> List[torch.Tensor]:
+             bucketed: bool = False, fp8=None) -> List[torch.Tensor]:
     """Continue every prompt by up to `max_new_tokens` ids; returns the new ids of each sequence (1-D
     int64 tensors on the CPU), ending with `eos_token_id` where the sequence produced it.
 
@@ -274,7 +328,10 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     it is an error.
 
     linear="skinny": the decode steps' projections run in `ops.skinny_linear` (at most 16 prompts; the
-    prefill keeps hipBLASLt).  decode="graph" (GPU only): the decode loop is captured into one HIP graph
+    prefill keeps hipBLASLt).  linear="skinny-fp8": they run in `ops.skinny_linear_fp8` on weight-only FP8
+    copies of the matrices (models/quantized.py).  The model is not modified and keeps its bf16 weights; the
+    prefill stays hipBLASLt in bf16 on the dequantised matrices, so the whole call computes one quantised
+    model.  `fp8` is an `Fp8DecodeWeights` of this model to reuse, None quantises the model for this call.  decode="graph" (GPU only): the decode loop is captured into one HIP graph
     per length bucket (`decode_bucket`) and replayed, see models/decode_graph.py; sampling then needs
     sampler="fused", whose draw counter lives on the device.  `decode` may also be a `GraphedDecode`
     built for this model, batch size and `s_max`: its graphs and cache are reused.  decode="eager" with
@@ -287,6 +344,8 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     if sampler not in ("torch", "fused"):
         raise ValueError(f"generate: sampler must be 'torch' or 'fused', got {sampler!r}")
     _check_linear(linear, len(prompts))
+    if linear != "skinny-fp8" and fp8 is not None:
+        raise ValueError(f'generate: fp8 weights were given with linear={linear!r}; they need linear="skinny-fp8"')
     graphed = not isinstance(decode, str)
     if not graphed and decode not in ("eager", "graph"):
         raise ValueError(f"generate: decode must be 'eager', 'graph' or a GraphedDecode, got {decode!r}")
@@ -325,8 +384,11 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     if graphed:
         from .decode_graph import GraphedDecode
 
-        gd = decode if isinstance(decode, GraphedDecode) else GraphedDecode(model, n, s_max, linear=linear)
+        gd = decode if isinstance(decode, GraphedDecode) else GraphedDecode(model, n, s_max, linear=linear, fp8=fp8)
+        if fp8 is not None and gd.fp8 is not fp8:
+            raise ValueError("generate: the GraphedDecode was captured with other fp8 weights")
         return gd.run(prompts, max_new_tokens, fused, seed, eos_token_id, s_max=s_max, linear=linear)
+    fp8 = _check_fp8(model, linear, fp8, build=True)
     gen = None
     if fused is not None:
         fused = {k: torch.tensor(v, dtype=torch.int32 if k == "top_k" else torch.float32, device=dev)
@@ -340,7 +402,7 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     out = torch.zeros(n, max_new_tokens, dtype=torch.long, device=dev)
     count = torch.zeros(n, dtype=torch.long, device=dev)  # ids kept per sequence
     done = torch.zeros(n, dtype=torch.bool, device=dev)
-    logits = prefill(model, prompts, cache)
+    logits = prefill(model, prompts, cache, fp8=fp8)
     for step in range(max_new_tokens):
         if fused is not None:
             nxt, _ = ops.sample_logits(logits, seed=int(seed), stream=stream, step=step_t, **fused)
@@ -355,6 +417,6 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
                 break
         if step + 1 < max_new_tokens:
             plan_len = decode_bucket(cache.max_len + 1, s_max) if bucketed else None
-            logits = decode_step(model, nxt, cache, linear=linear, plan_len=plan_len)
+            logits = decode_step(model, nxt, cache, linear=linear, plan_len=plan_len, fp8=fp8)
     out, count = out.cpu(), count.tolist()
     return [out[i, : count[i]].clone() for i in range(n)]

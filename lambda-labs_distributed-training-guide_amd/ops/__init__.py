@@ -28,11 +28,13 @@ from .functional import (  # noqa: E402
     layer_norm,
     linear,
     qk_norm_rope,
+    quantize_fp8_rows,
     rms_norm,
     rope,
     rope_tables,
     sample_logits,
     skinny_linear,
+    skinny_linear_fp8,
     swiglu,
     swiglu_mlp,
     vocab_parallel_fused_linear_cross_entropy,
@@ -61,5 +63,5 @@ __all__ = [
     "add_rms_norm", "attention", "rope", "embedding", "fused_linear_cross_entropy", "linear", "rms_norm",
     "rope_tables", "swiglu", "swiglu_mlp", "vocab_parallel_fused_linear_cross_entropy", "route_param_grad", "adamw_step",
     "fa_tuning", "layer_norm", "dropout_add_layer_norm", "gelu_mlp", "qk_norm_rope", "kv_cache_append", "decode_attention",
-    "sample_logits", "skinny_linear",
+    "sample_logits", "skinny_linear", "skinny_linear_fp8", "quantize_fp8_rows",
 ]

@@ -183,6 +183,40 @@ def skinny_linear(x, w, bias, act=0):
     return swiglu_fwd(y) if act else y
 
 
+def skinny_linear_fp8(x, wq, scale, bias, act=0):
+    """y = (x @ float(wq)^T) * scale (+ bias) at 1 <= M <= 16 rows: wq float8_e4m3fn [N, K], scale f32 [N];
+    f32 sums, one rounding; act = 1 as skinny_linear (csrc/kernels/skinny_gemm_fp8.hip).  Refuses what the
+    kernel refuses."""
+    name = "dtg: skinny_linear_fp8"
+    if x.dtype != torch.bfloat16:
+        raise RuntimeError(f"{name}: x must be a bf16 tensor")
+    if wq.dtype != torch.float8_e4m3fn:
+        raise RuntimeError(f"{name}: wq must be a float8_e4m3fn tensor")
+    if act not in (0, 1):
+        raise RuntimeError(f"{name}: act must be 0 (none) or 1 (SwiGLU)")
+    if x.dim() != 2 or not 1 <= x.shape[0] <= SKINNY_MAX_M:
+        raise RuntimeError(f"{name}: x must be [M, K] with 1 <= M <= {SKINNY_MAX_M}")
+    K = x.shape[1]
+    if K % 16:
+        raise RuntimeError(f"{name}: K must be a multiple of 16")
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+        raise RuntimeError(f"{name}: x must have unit inner stride and 16-B aligned rows")
+    if wq.dim() != 2 or wq.shape[1] != K or wq.shape[0] < 1 or not wq.is_contiguous() or wq.data_ptr() % 16:
+        raise RuntimeError(f"{name}: wq must be a contiguous 16-B aligned [N, K] on x's device")
+    N = wq.shape[0]
+    if scale.dtype != torch.float32 or scale.dim() != 1 or scale.shape[0] != N or not scale.is_contiguous():
+        raise RuntimeError(f"{name}: scale must be a contiguous f32 [N] on x's device")
+    if act and N % 2:
+        raise RuntimeError(f"{name}: the SwiGLU epilogue needs an even N (gate rows, then up rows)")
+    y = (x.float() @ wq.float().t()) * scale
+    if bias is not None:
+        if bias.dtype != torch.bfloat16 or bias.dim() != 1 or bias.shape[0] != N or not bias.is_contiguous():
+            raise RuntimeError(f"{name}: bias must be a contiguous bf16 [N]")
+        y = y + bias.float()
+    y = y.to(x.dtype)
+    return swiglu_fwd(y) if act else y
+
+
 def swiglu_bwd(dh, gu):
     inter = gu.shape[1] // 2
     g, u, d = gu[:, :inter].float(), gu[:, inter:].float(), dh.float()
@@ -800,6 +834,6 @@ for _name, _fn in list(globals().items()):
         "flash_attn_varlen_bwd", "flash_attn_fwd_drop", "flash_attn_bwd_drop", "flash_attn_bwd_qkv_drop", "philox_rng",
         "flash_attn_bwd_qkv_rope", "flash_attn_tuning", "layernorm_fwd", "dropout_add_layernorm_fwd", "layernorm_bwd",
         "gelu_fwd", "gelu_bwd", "gelu_bwd_t", "qk_norm_rope_fwd_", "qk_norm_rope_bwd_", "kv_cache_append_", "decode_attn",
-        "sample_logits", "skinny_linear",
+        "sample_logits", "skinny_linear", "skinny_linear_fp8",
     ):
         LIB.impl(_name, _fn, "CPU")

@@ -747,6 +747,87 @@ def skinny_linear(x, w, b=None, act=None):
     return ops.skinny_linear(x, w, b, act)
 
 
+# --------------------------------------------------------------------------------------------
+# Weight-only FP8 for the decode step (csrc/kernels/skinny_gemm_fp8.hip)
+# --------------------------------------------------------------------------------------------
+FP8_MAX = 448.0        # largest finite OCP e4m3fn magnitude
+FP8_MIN_SCALE_EXP = -100  # scales are floored at 2^-100
+
+
+def _pow2(k):
+    """2^k as f32 for an integer tensor k in [-126, 127], built from the exponent bits: exact on every device."""
+    return ((k.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+@torch.no_grad()
+def quantize_fp8_rows(w, pow2=True):
+    """Per-row weight quantisation to OCP e4m3fn (load time, torch ops): `w` bf16 / f32 [N, K] ->
+    (wq float8_e4m3fn [N, K] contiguous, scale f32 [N]) with w ~= float(wq) * scale[:, None].
+
+    pow2=True (default): scale[n] is the power of two that puts the row's largest magnitude into
+    (224, 448].  e4m3 is a floating-point format, so a power-of-two scale costs no relative precision, and
+    float(wq) * scale is exactly representable in bf16: the quantised matrix is exactly some bf16 matrix.
+    pow2=False: scale[n] = amax / 448.  An all-zero row gets scale 1; scales are floored at 2^-100.  torch's
+    cast to float8_e4m3fn does not saturate (465 becomes NaN), so the quotient is clamped to +-448 first:
+    the NaN codes 0x7f / 0xff are never emitted."""
+    if w.dim() != 2 or w.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"quantize_fp8_rows: w must be a bf16 or f32 [N, K] matrix, got {w.dtype} {tuple(w.shape)}")
+    w32 = w.detach().float()
+    amax = w32.abs().amax(dim=1) if w32.shape[1] else w32.new_zeros(w32.shape[0])
+    if not bool(torch.isfinite(amax).all()):
+        raise ValueError("quantize_fp8_rows: w holds non-finite values")
+    zero = amax == 0
+    if pow2:
+        # amax = m * 2^e with m in [0.5, 1); 448 = 0.875 * 2^9: m <= 0.875 -> amax / 2^(e - 9) in [256, 448],
+        # else amax / 2^(e - 8) in (224, 256).  frexp is exact; the quotient is checked all the same and the
+        # exponent moved by one step if it lies outside (224, 448].
+        m, e = torch.frexp(amax)
+        k = torch.where(m <= 0.875, e - 9, e - 8).to(torch.int32).clamp(FP8_MIN_SCALE_EXP, 127)
+        top = amax / _pow2(k)
+        k = torch.where(top > FP8_MAX, k + 1, torch.where((top <= FP8_MAX / 2) & ~zero, k - 1, k))
+        scale = _pow2(k.clamp(FP8_MIN_SCALE_EXP, 127))
+    else:
+        scale = (amax / FP8_MAX).clamp_min(2.0 ** FP8_MIN_SCALE_EXP)
+    scale = torch.where(zero, torch.ones_like(scale), scale)
+    wq = (w32 / scale[:, None]).clamp_(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn).contiguous()
+    return wq, scale.contiguous()
+
+
+@torch.no_grad()
+def skinny_linear_fp8(x, wq, scale, b=None, act=None):
+    """y = (x @ float(wq)^T) * scale (+ b) for 1 <= M <= 16 bf16 rows of x [M, K]: `ops.skinny_linear` with
+    the weights streamed as OCP e4m3fn bytes, `wq` float8_e4m3fn [N, K] and `scale` f32 [N] as
+    `quantize_fp8_rows` returns them.  f32 accumulation in a fixed order that does not depend on M, one
+    multiply by the scale after the reduction, then the bias, then one rounding.  act = "swiglu" (or 1) as
+    in `skinny_linear`: bitwise `swiglu(skinny_linear_fp8(x, wq, scale, b))`, in one launch."""
+    if act not in (None, 0, 1, "swiglu"):
+        raise ValueError(f"skinny_linear_fp8: act must be None or 'swiglu', got {act!r}")
+    act = 1 if act in (1, "swiglu") else 0
+    if x.dim() != 2 or wq.dim() != 2 or x.shape[1] != wq.shape[1]:
+        raise ValueError(f"skinny_linear_fp8: x [M, K] and wq [N, K] do not match: {tuple(x.shape)}, {tuple(wq.shape)}")
+    if scale.dim() != 1 or scale.shape[0] != wq.shape[0]:
+        raise ValueError(f"skinny_linear_fp8: scale must be [N = {wq.shape[0]}], got {tuple(scale.shape)}")
+    if x.shape[0] > SKINNY_MAX_M:
+        raise ValueError(f"skinny_linear_fp8: M = {x.shape[0]} rows exceed the kernel's limit of {SKINNY_MAX_M}")
+    if act and wq.shape[0] % 2:
+        raise ValueError(f"skinny_linear_fp8: the SwiGLU epilogue needs an even N, got {wq.shape[0]}")
+    if b is not None:
+        b = b.reshape(-1)
+    if x.is_cuda and not _SKINNY_FUSED:
+        y = torch.mm(x.float(), wq.float().t()) * scale
+        if b is not None:
+            y = y + b.float()
+        y = y.to(x.dtype)
+        if not act:
+            return y
+        inter = wq.shape[0] // 2
+        if inter % 8 == 0:
+            return ops.swiglu_fwd(y)
+        g, u = y[:, :inter].float(), y[:, inter:].float()  # widths the swiglu kernel does not take
+        return (F.silu(g) * u).to(y.dtype)
+    return ops.skinny_linear_fp8(x, wq, scale, b, act)
+
+
 def _mlp_backward(act, x, w1, w2, a, dy, b1=None, b2=None):
     """Backward of y = act(x @ w1^T (+ b1)) @ w2^T (+ b2) from the saved pre-activation a; `act`
     names the operators {act}_fwd / _bwd / _bwd_t.  Returns dx, dw1, dw2, db1, db2.

@@ -61,8 +61,9 @@ def main(argv=None):
     ap.add_argument("--sampler", choices=("torch", "fused"), default="torch",
                     help="torch: the chain of torch ops, one generator for the batch; fused: one HIP launch per step "
                     "with a counter-based draw per sequence (different ids for the same seed)")
-    ap.add_argument("--linear", choices=("blas", "skinny"), default="blas",
-                    help="decode-step projections: hipBLASLt, or the skinny-GEMM HIP kernel (at most 16 prompts)")
+    ap.add_argument("--linear", choices=("blas", "skinny", "skinny-fp8"), default="blas",
+                    help="decode-step projections: hipBLASLt, the skinny-GEMM HIP kernel, or that kernel on weight-only "
+                    "FP8 (e4m3, per-row scales) copies of the matrices, quantised at start (at most 16 prompts)")
     ap.add_argument("--decode", choices=("eager", "graph"), default="eager",
                     help="graph: capture the decode step into one HIP graph per length bucket and replay it (GPU; "
                     "sampling then needs --sampler fused)")
