@@ -23,6 +23,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .. import ops
+from ..ops.functional import SKINNY_MAX_M
 from .gpt2 import GPT2LMHeadModel
 from .llama import LlamaForCausalLM
 
@@ -59,14 +60,13 @@ class KVCache:
 
 
 LINEAR_MODES = ("blas", "skinny", "skinny-fp8")
-SKINNY_MAX_ROWS = 16  # = ops.functional.SKINNY_MAX_M: # sequences a decode step with linear="skinny" takes
 
 
 def _check_linear(linear, n=None):
     if linear not in LINEAR_MODES:
         raise ValueError(f"linear must be one of {LINEAR_MODES}, got {linear!r}")
-    if linear != "blas" and n is not None and n > SKINNY_MAX_ROWS:
-        raise ValueError(f'linear="{linear}" decodes at most {SKINNY_MAX_ROWS} sequences per step, got {n}')
+    if linear != "blas" and n is not None and n > SKINNY_MAX_M:
+        raise ValueError(f'linear="{linear}" decodes at most {SKINNY_MAX_M} sequences per step, got {n}')
 
 
 def _check_fp8(model, linear, fp8, build=False):
@@ -85,17 +85,47 @@ def _check_fp8(model, linear, fp8, build=False):
     return fp8
 
 
+def _projections(model, linear, fp8):
+    """The matrix products of one pass through the model, chosen once per call: proj(x, i, name, w, bias) is
+    the product with layer i's matrix `w`, which Fp8DecodeWeights calls `name`; mlp(x, i, m) the SwiGLU MLP `m`
+    of layer i; head(h) the LM head.  linear="skinny" (a decode step of at most 16 rows): ops.skinny_linear
+    instead of hipBLASLt, gate_up with its SwiGLU epilogue; linear="skinny-fp8": ops.skinny_linear_fp8 on the
+    e4m3 copies `fp8` (models/quantized.py; the bf16 kernel for a head without a copy).  linear="blas" with
+    `fp8` is the prefill of an FP8 run: hipBLASLt on the bf16 matrices the copies stand for (`fp8.dequantized`,
+    made where they are used and dropped), so the keys and values the prompt leaves in the cache belong to the
+    same quantised model as the decode steps that read them."""
+    fp8_head = fp8 is not None and fp8.has_head
+
+    if linear == "blas":
+        def proj(x, i, name, w, bias=None):
+            w = w if fp8 is None else fp8.dequantized(f"layers.{i}.{name}")
+            return ops.linear(x, w, None if bias is None else bias.view(-1))
+
+        def mlp(x, i, m):
+            if fp8 is None:
+                return m(x)
+            return ops.swiglu_mlp(x, fp8.dequantized(f"layers.{i}.mlp.gate_up_proj"), fp8.dequantized(f"layers.{i}.mlp.down_proj"))
+
+        def head(h):
+            return ops.linear(h, fp8.dequantized("lm_head") if fp8_head else model.lm_head_weight())
+    else:
+        def proj(x, i, name, w, bias=None, act=None):
+            if fp8 is None:
+                return ops.skinny_linear(x, w, bias, act)
+            return ops.skinny_linear_fp8(x, *fp8.layer(i, name), bias, act)
+
+        def mlp(x, i, m):
+            h = proj(x, i, "mlp.gate_up_proj", m.gate_up_proj.weight, act="swiglu")
+            return proj(h, i, "mlp.down_proj", m.down_proj.weight)
+
+        def head(h):
+            return ops.skinny_linear_fp8(h, *fp8.head()) if fp8_head else ops.skinny_linear(h, model.lm_head_weight())
+    return proj, mlp, head
+
+
 def _run_layers(model, x, append_and_attend, linear="blas", fp8=None):
-    """The decoder stack around a caller-supplied attention (qkv -> attention output).  linear="skinny"
-    (a decode step of at most 16 rows): the qkv, o, gate_up (+ SwiGLU) and down projections run in
-    ops.skinny_linear instead of hipBLASLt; linear="skinny-fp8": in ops.skinny_linear_fp8 on the e4m3
-    copies `fp8` (models/quantized.py).  linear="blas" with `fp8` is the prefill of an FP8 run: hipBLASLt on
-    the bf16 matrices the copies stand for (`fp8.dequantized`, made one at a time and dropped), so the keys and
-    values the prompt leaves in the cache belong to the same quantised model as the decode steps that read them."""
-    if linear == "skinny":
-        return _run_layers_skinny(model, x, append_and_attend)
-    if linear == "skinny-fp8":
-        return _run_layers_skinny_fp8(model, x, append_and_attend, fp8)
+    """The decoder stack around a caller-supplied attention (qkv -> attention output); see _projections."""
+    proj, mlp, _ = _projections(model, linear, fp8)
     res = None
     for i, layer in enumerate(model.layers):
         if res is None:
@@ -103,49 +133,10 @@ def _run_layers(model, x, append_and_attend, linear="blas", fp8=None):
         else:
             n, res = ops.add_rms_norm(x, res, layer.input_layernorm.weight, layer.eps)
         attn = layer.self_attn
-        b = getattr(attn.qkv_proj, "bias", None)
-        if fp8 is None:
-            w_qkv, w_o = attn.qkv_proj.weight, attn.o_proj.weight
-        else:
-            w_qkv, w_o = fp8.dequantized(f"layers.{i}.self_attn.qkv_proj"), fp8.dequantized(f"layers.{i}.self_attn.o_proj")
-        qkv = ops.linear(n, w_qkv, None if b is None else b.view(-1))
-        a = ops.linear(append_and_attend(i, attn, qkv), w_o)
+        qkv = proj(n, i, "self_attn.qkv_proj", attn.qkv_proj.weight, getattr(attn.qkv_proj, "bias", None))
+        a = proj(append_and_attend(i, attn, qkv), i, "self_attn.o_proj", attn.o_proj.weight)
         n2, res = ops.add_rms_norm(a, res, layer.post_attention_layernorm.weight, layer.eps)
-        if fp8 is None:
-            x = layer.mlp(n2)
-        else:
-            x = ops.swiglu_mlp(n2, fp8.dequantized(f"layers.{i}.mlp.gate_up_proj"), fp8.dequantized(f"layers.{i}.mlp.down_proj"))
-    return x, res
-
-
-def _run_layers_skinny(model, x, append_and_attend):
-    res = None
-    for i, layer in enumerate(model.layers):
-        if res is None:
-            n, res = ops.rms_norm(x, layer.input_layernorm.weight, layer.eps), x
-        else:
-            n, res = ops.add_rms_norm(x, res, layer.input_layernorm.weight, layer.eps)
-        attn, mlp = layer.self_attn, layer.mlp
-        qkv = ops.skinny_linear(n, attn.qkv_proj.weight, getattr(attn.qkv_proj, "bias", None))
-        a = ops.skinny_linear(append_and_attend(i, attn, qkv), attn.o_proj.weight)
-        n2, res = ops.add_rms_norm(a, res, layer.post_attention_layernorm.weight, layer.eps)
-        x = ops.skinny_linear(ops.skinny_linear(n2, mlp.gate_up_proj.weight, act="swiglu"), mlp.down_proj.weight)
-    return x, res
-
-
-def _run_layers_skinny_fp8(model, x, append_and_attend, fp8):
-    res = None
-    for i, layer in enumerate(model.layers):
-        if res is None:
-            n, res = ops.rms_norm(x, layer.input_layernorm.weight, layer.eps), x
-        else:
-            n, res = ops.add_rms_norm(x, res, layer.input_layernorm.weight, layer.eps)
-        attn = layer.self_attn
-        qkv = ops.skinny_linear_fp8(n, *fp8.layer(i, "self_attn.qkv_proj"), getattr(attn.qkv_proj, "bias", None))
-        a = ops.skinny_linear_fp8(append_and_attend(i, attn, qkv), *fp8.layer(i, "self_attn.o_proj"))
-        n2, res = ops.add_rms_norm(a, res, layer.post_attention_layernorm.weight, layer.eps)
-        h = ops.skinny_linear_fp8(n2, *fp8.layer(i, "mlp.gate_up_proj"), act="swiglu")
-        x = ops.skinny_linear_fp8(h, *fp8.layer(i, "mlp.down_proj"))
+        x = mlp(n2, i, layer.mlp)
     return x, res
 
 
@@ -162,11 +153,7 @@ def _append(attn, qkv, cache, i, cos, sin, pos, rows, pos_max):
 
 def _last_logits(model, x, res, linear="blas", fp8=None):
     h, _ = ops.add_rms_norm(x, res, model.norm.weight, model.config.rms_norm_eps)
-    if linear == "skinny-fp8" and fp8.has_head:
-        return ops.skinny_linear_fp8(h, *fp8.head())
-    if linear in ("skinny", "skinny-fp8"):
-        return ops.skinny_linear(h, model.lm_head_weight())
-    return ops.linear(h, fp8.dequantized("lm_head") if fp8 is not None and fp8.has_head else model.lm_head_weight())
+    return _projections(model, linear, fp8)[2](h)
 
 
 def _rows(cache, n, rows, device):

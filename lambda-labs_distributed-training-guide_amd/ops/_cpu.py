@@ -150,7 +150,36 @@ def swiglu_fwd(gu):
     return (F.silu(g) * u).to(gu.dtype)
 
 
-SKINNY_MAX_M = 16
+SKINNY_MAX_M = 16  # rows of x the skinny kernels are instantiated for (kSkinnyMaxM); imported where it is needed
+
+
+def _skinny_check(name, x, w, act, chunk, w_layout):
+    """The refusals the two skinny operators share; `chunk` = weights per 16-B load, `w_layout` the operator's
+    own message for the weight matrix."""
+    if x.dtype != torch.bfloat16:
+        raise RuntimeError(f"{name}: x must be a bf16 tensor")
+    if act not in (0, 1):
+        raise RuntimeError(f"{name}: act must be 0 (none) or 1 (SwiGLU)")
+    if x.dim() != 2 or not 1 <= x.shape[0] <= SKINNY_MAX_M:
+        raise RuntimeError(f"{name}: x must be [M, K] with 1 <= M <= {SKINNY_MAX_M}")
+    if x.shape[1] % chunk:
+        raise RuntimeError(f"{name}: K must be a multiple of {chunk}")
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+        raise RuntimeError(f"{name}: x must have unit inner stride and 16-B aligned rows")
+    if w.dim() != 2 or w.shape[1] != x.shape[1] or w.shape[0] < 1 or not w.is_contiguous() or w.data_ptr() % 16:
+        raise RuntimeError(f"{name}: {w_layout}")
+    if act and w.shape[0] % 2:
+        raise RuntimeError(f"{name}: the SwiGLU epilogue needs an even N (gate rows, then up rows)")
+
+
+def _skinny_tail(name, y, bias, act, dtype):
+    """f32 product [M, N] -> + bias, one rounding, swiglu_fwd when act."""
+    if bias is not None:
+        if bias.dtype != torch.bfloat16 or bias.dim() != 1 or bias.shape[0] != y.shape[1] or not bias.is_contiguous():
+            raise RuntimeError(f"{name}: bias must be a contiguous bf16 [N]")
+        y = y + bias.float()
+    y = y.to(dtype)
+    return swiglu_fwd(y) if act else y
 
 
 def skinny_linear(x, w, bias, act=0):
@@ -160,61 +189,21 @@ def skinny_linear(x, w, bias, act=0):
     name = "dtg: skinny_linear"
     if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
         raise RuntimeError(f"{name}: x and w must be bf16 tensors")
-    if act not in (0, 1):
-        raise RuntimeError(f"{name}: act must be 0 (none) or 1 (SwiGLU)")
-    if x.dim() != 2 or not 1 <= x.shape[0] <= SKINNY_MAX_M:
-        raise RuntimeError(f"{name}: x must be [M, K] with 1 <= M <= {SKINNY_MAX_M}")
-    K = x.shape[1]
-    if K % 8:
-        raise RuntimeError(f"{name}: K must be a multiple of 8")
-    if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
-        raise RuntimeError(f"{name}: x must have unit inner stride and 16-B aligned rows")
-    if w.dim() != 2 or w.shape[1] != K or w.shape[0] < 1 or not w.is_contiguous():
-        raise RuntimeError(f"{name}: w must be a contiguous [N, K] on x's device")
-    N = w.shape[0]
-    if act and N % 2:
-        raise RuntimeError(f"{name}: the SwiGLU epilogue needs an even N (gate rows, then up rows)")
-    y = x.float() @ w.float().t()
-    if bias is not None:
-        if bias.dtype != torch.bfloat16 or bias.dim() != 1 or bias.shape[0] != N or not bias.is_contiguous():
-            raise RuntimeError(f"{name}: bias must be a contiguous bf16 [N]")
-        y = y + bias.float()
-    y = y.to(x.dtype)
-    return swiglu_fwd(y) if act else y
+    _skinny_check(name, x, w, act, 8, "w must be a contiguous [N, K] on x's device")
+    return _skinny_tail(name, x.float() @ w.float().t(), bias, act, x.dtype)
 
 
 def skinny_linear_fp8(x, wq, scale, bias, act=0):
     """y = (x @ float(wq)^T) * scale (+ bias) at 1 <= M <= 16 rows: wq float8_e4m3fn [N, K], scale f32 [N];
-    f32 sums, one rounding; act = 1 as skinny_linear (csrc/kernels/skinny_gemm_fp8.hip).  Refuses what the
+    f32 sums, one rounding; act = 1 as skinny_linear (csrc/kernels/skinny_gemm.hip).  Refuses what the
     kernel refuses."""
     name = "dtg: skinny_linear_fp8"
-    if x.dtype != torch.bfloat16:
-        raise RuntimeError(f"{name}: x must be a bf16 tensor")
     if wq.dtype != torch.float8_e4m3fn:
         raise RuntimeError(f"{name}: wq must be a float8_e4m3fn tensor")
-    if act not in (0, 1):
-        raise RuntimeError(f"{name}: act must be 0 (none) or 1 (SwiGLU)")
-    if x.dim() != 2 or not 1 <= x.shape[0] <= SKINNY_MAX_M:
-        raise RuntimeError(f"{name}: x must be [M, K] with 1 <= M <= {SKINNY_MAX_M}")
-    K = x.shape[1]
-    if K % 16:
-        raise RuntimeError(f"{name}: K must be a multiple of 16")
-    if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
-        raise RuntimeError(f"{name}: x must have unit inner stride and 16-B aligned rows")
-    if wq.dim() != 2 or wq.shape[1] != K or wq.shape[0] < 1 or not wq.is_contiguous() or wq.data_ptr() % 16:
-        raise RuntimeError(f"{name}: wq must be a contiguous 16-B aligned [N, K] on x's device")
-    N = wq.shape[0]
-    if scale.dtype != torch.float32 or scale.dim() != 1 or scale.shape[0] != N or not scale.is_contiguous():
+    _skinny_check(name, x, wq, act, 16, "wq must be a contiguous 16-B aligned [N, K] on x's device")
+    if scale.dtype != torch.float32 or scale.dim() != 1 or scale.shape[0] != wq.shape[0] or not scale.is_contiguous():
         raise RuntimeError(f"{name}: scale must be a contiguous f32 [N] on x's device")
-    if act and N % 2:
-        raise RuntimeError(f"{name}: the SwiGLU epilogue needs an even N (gate rows, then up rows)")
-    y = (x.float() @ wq.float().t()) * scale
-    if bias is not None:
-        if bias.dtype != torch.bfloat16 or bias.dim() != 1 or bias.shape[0] != N or not bias.is_contiguous():
-            raise RuntimeError(f"{name}: bias must be a contiguous bf16 [N]")
-        y = y + bias.float()
-    y = y.to(x.dtype)
-    return swiglu_fwd(y) if act else y
+    return _skinny_tail(name, (x.float() @ wq.float().t()) * scale, bias, act, x.dtype)
 
 
 def swiglu_bwd(dh, gu):

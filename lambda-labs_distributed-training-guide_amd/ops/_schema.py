@@ -53,7 +53,7 @@ _DEFS = [
     # (unit inner stride, 16-B aligned rows), w bf16 [N, K] contiguous, K % 8 == 0, f32 accumulation, one
     # rounding; act = 1: w = gate rows then up rows, returns swiglu_fwd of that product, [M, N / 2]
     "skinny_linear(Tensor x, Tensor w, Tensor? bias, int act=0) -> Tensor",
-    # the same with weight-only FP8 (csrc/kernels/skinny_gemm_fp8.hip): wq float8_e4m3fn (OCP) [N, K]
+    # the same with weight-only FP8 (the same kernel, its e4m3 weight format): wq float8_e4m3fn (OCP) [N, K]
     # contiguous, K % 16 == 0, scale f32 [N] (one per weight row): y = (x @ float(wq)^T) * scale (+ bias)
     "skinny_linear_fp8(Tensor x, Tensor wq, Tensor scale, Tensor? bias, int act=0) -> Tensor",
     "swiglu_fwd(Tensor gu) -> Tensor",

@@ -12,6 +12,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from . import grad_routing as _gr
+from ._cpu import SKINNY_MAX_M
 from .grad_routing import route_embedding_grad, route_param_grad, route_weight_grad_mm
 
 ops = torch.ops.dtg
@@ -714,7 +715,32 @@ def swiglu(gu):
 # Inference only (no autograd).  DTG_SKINNY_FUSED=0 composes the same function from torch.mm / addmm
 # (hipBLASLt) and ops.swiglu: the kernel's A/B partner; so do, on a GPU, dtypes other than bf16.
 _SKINNY_FUSED = os.environ.get("DTG_SKINNY_FUSED", "1") == "1"
-SKINNY_MAX_M = 16  # rows the kernel is instantiated for
+
+
+def _skinny_args(name, x, w, b, act, wname="w"):
+    """What skinny_linear and skinny_linear_fp8 (`name`) share in argument handling; returns act as 0 / 1 and
+    the bias as [N] or None."""
+    if act not in (None, 0, 1, "swiglu"):
+        raise ValueError(f"{name}: act must be None or 'swiglu', got {act!r}")
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"{name}: x [M, K] and {wname} [N, K] do not match: {tuple(x.shape)}, {tuple(w.shape)}")
+    if x.shape[0] > SKINNY_MAX_M:
+        raise ValueError(f"{name}: M = {x.shape[0]} rows exceed the kernel's limit of {SKINNY_MAX_M}")
+    act = 1 if act in (1, "swiglu") else 0
+    if act and w.shape[0] % 2:
+        raise ValueError(f"{name}: the SwiGLU epilogue needs an even N, got {w.shape[0]}")
+    return act, None if b is None else b.reshape(-1)
+
+
+def _skinny_composed_tail(y, act):
+    """The composed (DTG_SKINNY_FUSED=0) path after the rounded product y [M, N]: its SwiGLU when act."""
+    if not act:
+        return y
+    inter = y.shape[1] // 2
+    if inter % 8 == 0:
+        return ops.swiglu_fwd(y)
+    g, u = y[:, :inter].float(), y[:, inter:].float()  # widths the swiglu kernel does not take
+    return (F.silu(g) * u).to(y.dtype)
 
 
 @torch.no_grad()
@@ -724,31 +750,14 @@ def skinny_linear(x, w, b=None, act=None):
     gate rows, then the up rows (LlamaMLP.gate_up_proj); the result is swiglu(x @ w^T (+ b)), [M, N / 2],
     bitwise what `swiglu(skinny_linear(x, w, b))` returns, in one launch.  f32 accumulation in a fixed
     order that does not depend on M: a row's result is the same alone and inside a batch."""
-    if act not in (None, 0, 1, "swiglu"):
-        raise ValueError(f"skinny_linear: act must be None or 'swiglu', got {act!r}")
-    act = 1 if act in (1, "swiglu") else 0
-    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
-        raise ValueError(f"skinny_linear: x [M, K] and w [N, K] do not match: {tuple(x.shape)}, {tuple(w.shape)}")
-    if x.shape[0] > SKINNY_MAX_M:
-        raise ValueError(f"skinny_linear: M = {x.shape[0]} rows exceed the kernel's limit of {SKINNY_MAX_M}")
-    if act and w.shape[0] % 2:
-        raise ValueError(f"skinny_linear: the SwiGLU epilogue needs an even N, got {w.shape[0]}")
-    if b is not None:
-        b = b.reshape(-1)
+    act, b = _skinny_args("skinny_linear", x, w, b, act)
     if x.is_cuda and not (_SKINNY_FUSED and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16):
-        y = torch.mm(x, w.t()) if b is None else torch.addmm(b, x, w.t())
-        if not act:
-            return y
-        inter = w.shape[0] // 2
-        if inter % 8 == 0:
-            return ops.swiglu_fwd(y)
-        g, u = y[:, :inter].float(), y[:, inter:].float()  # widths the swiglu kernel does not take
-        return (F.silu(g) * u).to(y.dtype)
+        return _skinny_composed_tail(torch.mm(x, w.t()) if b is None else torch.addmm(b, x, w.t()), act)
     return ops.skinny_linear(x, w, b, act)
 
 
 # --------------------------------------------------------------------------------------------
-# Weight-only FP8 for the decode step (csrc/kernels/skinny_gemm_fp8.hip)
+# Weight-only FP8 for the decode step (csrc/kernels/skinny_gemm.hip, the e4m3 weight format)
 # --------------------------------------------------------------------------------------------
 FP8_MAX = 448.0        # largest finite OCP e4m3fn magnitude
 FP8_MIN_SCALE_EXP = -100  # scales are floored at 2^-100
@@ -800,31 +809,14 @@ def skinny_linear_fp8(x, wq, scale, b=None, act=None):
     `quantize_fp8_rows` returns them.  f32 accumulation in a fixed order that does not depend on M, one
     multiply by the scale after the reduction, then the bias, then one rounding.  act = "swiglu" (or 1) as
     in `skinny_linear`: bitwise `swiglu(skinny_linear_fp8(x, wq, scale, b))`, in one launch."""
-    if act not in (None, 0, 1, "swiglu"):
-        raise ValueError(f"skinny_linear_fp8: act must be None or 'swiglu', got {act!r}")
-    act = 1 if act in (1, "swiglu") else 0
-    if x.dim() != 2 or wq.dim() != 2 or x.shape[1] != wq.shape[1]:
-        raise ValueError(f"skinny_linear_fp8: x [M, K] and wq [N, K] do not match: {tuple(x.shape)}, {tuple(wq.shape)}")
+    act, b = _skinny_args("skinny_linear_fp8", x, wq, b, act, wname="wq")
     if scale.dim() != 1 or scale.shape[0] != wq.shape[0]:
         raise ValueError(f"skinny_linear_fp8: scale must be [N = {wq.shape[0]}], got {tuple(scale.shape)}")
-    if x.shape[0] > SKINNY_MAX_M:
-        raise ValueError(f"skinny_linear_fp8: M = {x.shape[0]} rows exceed the kernel's limit of {SKINNY_MAX_M}")
-    if act and wq.shape[0] % 2:
-        raise ValueError(f"skinny_linear_fp8: the SwiGLU epilogue needs an even N, got {wq.shape[0]}")
-    if b is not None:
-        b = b.reshape(-1)
     if x.is_cuda and not _SKINNY_FUSED:
         y = torch.mm(x.float(), wq.float().t()) * scale
         if b is not None:
             y = y + b.float()
-        y = y.to(x.dtype)
-        if not act:
-            return y
-        inter = wq.shape[0] // 2
-        if inter % 8 == 0:
-            return ops.swiglu_fwd(y)
-        g, u = y[:, :inter].float(), y[:, inter:].float()  # widths the swiglu kernel does not take
-        return (F.silu(g) * u).to(y.dtype)
+        return _skinny_composed_tail(y.to(x.dtype), act)
     return ops.skinny_linear_fp8(x, wq, scale, b, act)
 
 

@@ -1,4 +1,4 @@
-"""ops.skinny_linear_fp8 on the gfx950 kernel (csrc/kernels/skinny_gemm_fp8.hip): every e4m3 code bit for bit,
+"""ops.skinny_linear_fp8 on the gfx950 kernel (csrc/kernels/skinny_gemm.hip): every e4m3 code bit for bit,
 the f64 bound at every edge of the tiling, the SwiGLU epilogue against swiglu_fwd bit for bit, row invariance,
 unread memory, refusals and the composed path; ops.quantize_fp8_rows on the device against the CPU."""
 import pytest

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""ops.skinny_linear (csrc/kernels/skinny_gemm.hip) and ops.skinny_linear_fp8 (skinny_gemm_fp8.hip, weight-only
+"""ops.skinny_linear (csrc/kernels/skinny_gemm.hip) and ops.skinny_linear_fp8 (the same kernel, weight-only
 e4m3) against hipBLASLt (torch.mm / addmm, + ops.swiglu for the gate_up projection) in the same process, at
 the decode-step projection shapes of Llama-3-8B and M = 1, 4, 8, 16 rows: time per call from HIP events and
 the rate at which the weight bytes are consumed (the FP8 arm's GB/s counts its one-byte weights).
