@@ -81,8 +81,11 @@ inline KvPlan plan_kv(const Call& c, const Tuning& t) {
   const Variant var = variant(c);
   // Items staged ahead (Tuning::kv_pf).  Equal on MI355X once the kernel's false vmcnt waits were
   // gone (bwd 0.767 vs 0.768 ms at the 8B shape, profiles/r1_s51_*), so the single-set form with
-  // fewer registers is the default; dropout and sliding windows have only that form.
-  const int pf = var == Variant::PLAIN ? t.kv_pf : 1;
+  // fewer registers is the default; dropout and sliding windows have only that form.  Key ranges
+  // take it too: a range with keys but no queries (context parallelism emits them) gives a key
+  // block zero items, and the two-ahead prologue loads items 0 and 1 unconditionally -- item
+  // indices it divides by the per-head item count, 0 there.  The single-set loop loads nothing.
+  const int pf = var == Variant::PLAIN && !c.key_ranges ? t.kv_pf : 1;
   // Query rows per item (Tuning::kv_qb).  64 (the two-half software pipeline) is the default:
   // backward 2-4 % faster on every benchmarked shape, -1.9 ms per 8B step (profiles/r3_s39).
   // Dropout always uses it; sliding windows and the two-item prefetch keep 32.

@@ -632,10 +632,10 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, k_start, k_len, max_seqlen_q, m
     return o.to(q.dtype), lse
 
 
-def flash_attn_bwd(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, causal, window=0, k_start=None, k_len=None):
-    """The kernel's semantics: P = exp(S*scale - lse) with the GIVEN lse, delta = rowsum(dO*O)
-    with the GIVEN o (so a block of a larger softmax -- context parallelism -- gets the
-    gradient of the full softmax)."""
+def _flash_attn_bwd_f32(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, causal, window=0, k_start=None,
+                        k_len=None):
+    """flash_attn_bwd's dq, dk, dv in f32, before the store's rounding (the fused RoPE form rotates
+    them first, as the kernel epilogues do)."""
     T, hq, d = q.shape
     _check_attn_inputs(q, k, v)
     # the HIP entry point's layout contract (csrc/kernels/flash_attn.hip), checked here too so the
@@ -671,6 +671,14 @@ def flash_attn_bwd(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, causal,
         dq[a:b] = dqh.transpose(0, 1)
         dk[ka:kb] += dkh.view(hkv, rep, kb - ka, d).sum(1).transpose(0, 1)
         dv[ka:kb] += dvh.view(hkv, rep, kb - ka, d).sum(1).transpose(0, 1)
+    return dq, dk, dv
+
+
+def flash_attn_bwd(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, causal, window=0, k_start=None, k_len=None):
+    """The kernel's semantics: P = exp(S*scale - lse) with the GIVEN lse, delta = rowsum(dO*O)
+    with the GIVEN o (so a block of a larger softmax -- context parallelism -- gets the
+    gradient of the full softmax)."""
+    dq, dk, dv = _flash_attn_bwd_f32(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, causal, window, k_start, k_len)
     return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
 
 
@@ -688,9 +696,13 @@ def flash_attn_bwd_qkv(dout, qkv, nq, nkv, head_dim, o, lse, cu_seqlens, max_seq
 
 def flash_attn_bwd_qkv_rope(dout, qkv, nq, nkv, head_dim, o, lse, cu_seqlens, max_seqlen, scale, causal, cos, sin,
                             pos, window=0):
-    dqkv = flash_attn_bwd_qkv(dout, qkv, nq, nkv, head_dim, o, lse, cu_seqlens, max_seqlen, scale, causal, window)
+    # as the kernels' epilogues: the inverse rotation in f32, then the single rounding of the store
+    T = qkv.shape[0]
+    q, k, v = _qkv_heads(qkv, nq, nkv, head_dim)
+    dq, dk, dv = _flash_attn_bwd_f32(dout, q, k, v, o, lse, cu_seqlens, max_seqlen, scale, causal, window)
+    dqkv = torch.cat([dq.reshape(T, -1), dk.reshape(T, -1), dv.reshape(T, -1)], dim=1)
     rope_(dqkv, cos, sin, pos, nq + nkv, head_dim, True)
-    return dqkv
+    return dqkv.to(qkv.dtype)
 
 
 def swiglu_bwd_t(dh, gu):

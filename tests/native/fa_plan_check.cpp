@@ -132,6 +132,9 @@ int main() {
   expect_kv("kv 128 window non-causal", call(128, false, 64), dflt, PLAIN, false, 1, 64, 4, 8, 66560);
   expect_kv("kv 128 key ranges: no split", call(128, true, 0, false, true), dflt, PLAIN, true, 1, 64, 1, 2, 66560);
   expect_kv("kv 64 key ranges qb 32", call(64, false, 0, false, true), qb32, PLAIN, false, 1, 32, 1, 2, 16896);
+  // key ranges never take the two-ahead prefetch (a range with keys and no queries has zero items)
+  expect_kv("kv 128 key ranges pf 2: PF 1, qb 32", call(128, true, 0, false, true), pf2, PLAIN, true, 1, 32, 1, 2, 33280);
+  expect_kv("kv 64 key ranges pf 2 non-causal", call(64, false, 0, false, true), pf2qb32, PLAIN, false, 1, 32, 1, 2, 16896);
   expect_kv("kv 128 dropout", call(128, true, 0, true), dflt, DROP, true, 1, 64, 4, 8, 66560);
   expect_kv("kv 64 dropout non-causal", call(64, false, 0, true), dflt, DROP, false, 1, 64, 4, 8, 33792);
   expect_kv("kv 128 dropout qb 32", call(128, true, 0, true), qb32, DROP, true, 1, 64, 4, 8, 66560);
