@@ -25,6 +25,14 @@
 // max = -inf, sum = 0; every exp(m - m_new) is guarded by m == -inf, so the empty partial
 // contributes 0 instead of exp(-inf + inf) = NaN.  Keys outside the attended range are never
 // loaded (the cache may hold anything there, NaN included).
+//
+// decode_attn_multi: Q new tokens per sequence (speculative verification), one attended length per token.
+// The same kernel template with a query tile: grid (sequence x query tile, kv head, split), a workgroup
+// serves decode::q_tile(G) consecutive tokens times the G heads, so a K / V piece is loaded once for up
+// to 16 (token, head) pairs.  Partials and output are indexed with the token in the place of the
+// sequence, so decode_combine_kernel serves unchanged.  At window 0 a token's output row is, bit for bit,
+// decode_attn's for that token alone with the same max_len and splits.  Keys past the largest length of
+// a tile's tokens are never loaded; keys between its tokens' ranges are (they score -inf).
 #include "decode_attn_plan.h"
 #include "rope_common.h"
 
@@ -78,44 +86,75 @@ __global__ __launch_bounds__(256) void kv_append_kernel(
   }
 }
 
-template <int D, int G>
+// QT = 1 is decode_attn; QT > 1 serves decode_attn_multi: a tile of QT consecutive tokens of sequence b
+// (tokens t0 .. t0 + QT - 1 of its Q, row b * Q + t of qkv / lens) shares the workgroup's K / V stream.
+// The QT * G (token, head) pairs are laid out as the G heads of the one-token form; a pair's arithmetic
+// is that form's, expression for expression.  The key loop starts at the smallest k0 of the tile's
+// tokens that hold keys in this split (all equal split * chunk without a window, so key j sits in the
+// same lane whatever the query) and runs to their largest k1; a key outside a token's own [k0, k1)
+// scores -inf for it, which leaves its (m, l, acc) as they were: alpha = exp(m - m) = 1, p = 0.
+template <int D, int G, int QT>
 __global__ __launch_bounds__(decode::kThreads) void decode_attn_kernel(
     const uint16_t* __restrict__ qkv, int64_t q_stride, const uint16_t* __restrict__ kc,
     const uint16_t* __restrict__ vc, const int32_t* __restrict__ rows, const int32_t* __restrict__ lens,
     float* __restrict__ ws_o, float* __restrict__ ws_ml, uint16_t* __restrict__ out, int nkv, int splits,
-    int64_t chunk, int64_t window, int64_t rows_max, int64_t S_max, float scale) {
+    int64_t chunk, int64_t window, int64_t rows_max, int64_t S_max, float scale, int Q) {
+  // Every multiply-add below is written out (fmaf, or a product and a sum that stay apart): left to the
+  // compiler, which products fuse with which sums differed from element to element and from one
+  // instantiation to the next, and the bits of the QT > 1 forms would not be those of QT = 1.
+#pragma clang fp contract(off)
   constexpr int LPK = D / 8;                      // lanes per key
   constexpr int KPW = kWave / LPK;                // keys per wave per load
   constexpr int NW = decode::kThreads / kWave;    // waves
   constexpr int KSTEP = NW * KPW;                 // keys per workgroup per load
   constexpr int UN = decode::kKeyTile / KSTEP;    // loads in flight per lane and tensor
+  constexpr int H = QT * G;                       // (token, head) pairs of the workgroup
   static_assert(UN >= 1 && UN * KSTEP == decode::kKeyTile, "key tile");
-  __shared__ float sm_o[NW][G][D];
-  __shared__ float sm_m[NW][G], sm_l[NW][G];
+  static_assert(H <= decode::kMaxPairs, "register budget");
+  __shared__ float sm_o[NW][H][D];
+  __shared__ float sm_m[NW][H], sm_l[NW][H];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, sub = lane / LPK, li = lane % LPK;
   const int split = blockIdx.x % splits;
   const int h = (blockIdx.x / splits) % nkv;
-  const int64_t b = blockIdx.x / ((int64_t)splits * nkv);
+  const int64_t z = blockIdx.x / ((int64_t)splits * nkv);
+  const int qtiles = (Q + QT - 1) / QT;
+  const int64_t b = z / qtiles;
+  const int t0 = (int)(z % qtiles) * QT;
   const int64_t row = rows[b];
-  int64_t len = lens[b];
-  if (row < 0 || row >= rows_max || len < 0) len = 0;
-  if (len > S_max) len = S_max;
-  const int64_t lo = window > 0 && len > window ? len - window : 0;
-  const int64_t k0 = lo > split * chunk ? lo : split * chunk;
-  // the last split runs to the end of the row even if max_len understated it: slow, never wrong
-  const int64_t k1 = split == splits - 1 || len < (split + 1) * chunk ? len : (split + 1) * chunk;
-
-  float q[G][8], acc[G][8], m[G], l[G];
+  // per token: its attended keys of this split, [tk0, tk1); the workgroup walks [k0, k1), their hull
+  int64_t tk0[QT], tk1[QT], k0 = S_max, k1 = 0;
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
-    load8(qkv + b * q_stride + ((int64_t)h * G + g) * D + li * 8, q[g]);
-    m[g] = -INFINITY;
-    l[g] = 0.f;
+  for (int t = 0; t < QT; ++t) {
+    int64_t len = t0 + t < Q ? lens[b * Q + t0 + t] : 0;
+    if (row < 0 || row >= rows_max || len < 0) len = 0;
+    if (len > S_max) len = S_max;
+    const int64_t lo = window > 0 && len > window ? len - window : 0;
+    tk0[t] = lo > split * chunk ? lo : split * chunk;
+    // the last split runs to the end of the row even if max_len understated it: slow, never wrong
+    tk1[t] = split == splits - 1 || len < (split + 1) * chunk ? len : (split + 1) * chunk;
+    if (tk1[t] > tk0[t]) {
+      k0 = tk0[t] < k0 ? tk0[t] : k0;
+      k1 = tk1[t] > k1 ? tk1[t] : k1;
+    }
+  }
+
+  float q[H][8], acc[H][8], m[H], l[H];
+#pragma unroll
+  for (int x = 0; x < H; ++x) {
+    const int t = x / G, g = x % G;
+    if (QT == 1 || t0 + t < Q) {
+      load8(qkv + (b * Q + t0 + t) * q_stride + ((int64_t)h * G + g) * D + li * 8, q[x]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) q[x][i] = 0.f;
+    }
+    m[x] = -INFINITY;
+    l[x] = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      q[g][i] *= scale;
-      acc[g][i] = 0.f;
+      q[x][i] *= scale;
+      acc[x][i] = 0.f;
     }
   }
 
@@ -124,31 +163,33 @@ __global__ __launch_bounds__(decode::kThreads) void decode_attn_kernel(
   const uint16_t* vb = vc + head_off;
   for (int64_t j0 = k0; j0 < k1; j0 += decode::kKeyTile) {
     u16x8 kr[UN], vr[UN];
-    bool ok[UN];
+    unsigned ok[UN];  // bit t: token t of the tile attends the key
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       const int64_t j = j0 + u * KSTEP + wave * KPW + sub;
-      ok[u] = j < k1;
+      ok[u] = 0;
+#pragma unroll
+      for (int t = 0; t < QT; ++t) ok[u] |= (unsigned)(j >= tk0[t] && j < tk1[t]) << t;
       kr[u] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
       vr[u] = kr[u];
-      if (ok[u]) {
+      if (QT == 1 ? ok[u] != 0 : j < k1) {  // the hull: a key between two tokens' ranges is loaded
         kr[u] = *reinterpret_cast<const u16x8*>(kb + j * D);
         vr[u] = *reinterpret_cast<const u16x8*>(vb + j * D);
       }
     }
-    float sc[UN][G];
+    float sc[UN][H];
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       float kf[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) kf[i] = bf2f(kr[u][i]);
 #pragma unroll
-      for (int g = 0; g < G; ++g) {
+      for (int x = 0; x < H; ++x) {
         float d = 0.f;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) d += q[g][i] * kf[i];
+        for (int i = 0; i < 8; ++i) d = fmaf(q[x][i], kf[i], d);
         d = lanes_sum<LPK>(d);
-        sc[u][g] = ok[u] ? d : -INFINITY;
+        sc[u][x] = (ok[u] >> (x / G)) & 1u ? d : -INFINITY;
       }
     }
     float vf[UN][8];
@@ -157,64 +198,65 @@ __global__ __launch_bounds__(decode::kThreads) void decode_attn_kernel(
 #pragma unroll
       for (int i = 0; i < 8; ++i) vf[u][i] = bf2f(vr[u][i]);
 #pragma unroll
-    for (int g = 0; g < G; ++g) {
-      float mn = m[g];
+    for (int x = 0; x < H; ++x) {
+      float mn = m[x];
 #pragma unroll
-      for (int u = 0; u < UN; ++u) mn = fmaxf(mn, sc[u][g]);
-      const float alpha = rescale(m[g], mn);
+      for (int u = 0; u < UN; ++u) mn = fmaxf(mn, sc[u][x]);
+      const float alpha = rescale(m[x], mn);
       float p[UN], ps = 0.f;
 #pragma unroll
       for (int u = 0; u < UN; ++u) {
-        p[u] = rescale(sc[u][g], mn);
+        p[u] = rescale(sc[u][x], mn);
         ps += p[u];
       }
-      m[g] = mn;
-      l[g] = l[g] * alpha + ps;
+      m[x] = mn;
+      l[x] = fmaf(l[x], alpha, ps);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        float a = acc[g][i] * alpha;
+        float a = acc[x][i] * alpha;
 #pragma unroll
-        for (int u = 0; u < UN; ++u) a += p[u] * vf[u][i];
-        acc[g][i] = a;
+        for (int u = 0; u < UN; ++u) a = fmaf(p[u], vf[u][i], a);
+        acc[x][i] = a;
       }
     }
   }
 
   // merge the lane groups of the wave (butterfly over the group index), then the waves through LDS
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
+  for (int x = 0; x < H; ++x) {
 #pragma unroll
     for (int o = LPK; o < kWave; o <<= 1) {
-      const float mo = __shfl_xor(m[g], o, kWave), lo_ = __shfl_xor(l[g], o, kWave);
-      const float mn = fmaxf(m[g], mo);
-      const float a = rescale(m[g], mn), bw = rescale(mo, mn);
-      l[g] = l[g] * a + lo_ * bw;
+      const float mo = __shfl_xor(m[x], o, kWave), lo_ = __shfl_xor(l[x], o, kWave);
+      const float mn = fmaxf(m[x], mo);
+      const float a = rescale(m[x], mn), bw = rescale(mo, mn);
+      l[x] = fmaf(l[x], a, lo_ * bw);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) acc[g][i] = acc[g][i] * a + __shfl_xor(acc[g][i], o, kWave) * bw;
-      m[g] = mn;
+      for (int i = 0; i < 8; ++i) acc[x][i] = fmaf(acc[x][i], a, __shfl_xor(acc[x][i], o, kWave) * bw);
+      m[x] = mn;
     }
     if (sub == 0) {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) sm_o[wave][g][li * 8 + i] = acc[g][i];
+      for (int i = 0; i < 8; ++i) sm_o[wave][x][li * 8 + i] = acc[x][i];
       if (li == 0) {
-        sm_m[wave][g] = m[g];
-        sm_l[wave][g] = l[g];
+        sm_m[wave][x] = m[x];
+        sm_l[wave][x] = l[x];
       }
     }
   }
   __syncthreads();
-  const int64_t bh = b * nkv + h;
-  for (int e = tid; e < G * D; e += decode::kThreads) {
-    const int g = e / D, d = e % D;
+  for (int e = tid; e < H * D; e += decode::kThreads) {
+    const int x = e / D, d = e % D, t = x / G, g = x % G;
+    if (QT > 1 && t0 + t >= Q) break;  // the tile's tokens past Q (x grows with e)
+    const int64_t bh = (b * Q + t0 + t) * nkv + h;
     float mn = -INFINITY;
 #pragma unroll
-    for (int w = 0; w < NW; ++w) mn = fmaxf(mn, sm_m[w][g]);
+    for (int w = 0; w < NW; ++w) mn = fmaxf(mn, sm_m[w][x]);
     float o = 0.f, ls = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; ++w) {
-      const float wt = rescale(sm_m[w][g], mn);
-      o += sm_o[w][g][d] * wt;
-      ls += sm_l[w][g] * wt;
+      const float wt = rescale(sm_m[w][x], mn);
+      o = fmaf(sm_o[w][x][d], wt, o);
+      ls = fmaf(sm_l[w][x], wt, ls);
     }
     if (splits == 1) {
       out[(bh * G + g) * D + d] = f2bf(ls > 0.f ? o / ls : 0.f);
@@ -265,9 +307,9 @@ void check_qkv(const at::Tensor& qkv, int64_t nq, int64_t nkv, int64_t D, const 
   rope::check_qkv(qkv, nq + 2 * nkv, D, name);
 }
 
-void check_index(const at::Tensor& t, int64_t n, const char* name, const char* what) {
+void check_index(const at::Tensor& t, int64_t n, const char* name, const char* what, const char* per = "token") {
   DTG_CHECK(t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous() && t.numel() == n, name, ": ", what,
-            " must be an int32 GPU tensor with one entry per token");
+            " must be an int32 GPU tensor with one entry per ", per);
 }
 
 }  // namespace
@@ -297,64 +339,94 @@ void kv_cache_append_(const at::Tensor& qkv, const at::Tensor& k_cache, const at
   DTG_LAUNCH_CHECK();
 }
 
-at::Tensor decode_attn(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                       const at::Tensor& rows, const at::Tensor& lens, int64_t nq, int64_t nkv, int64_t head_dim,
-                       double scale, int64_t max_len, int64_t window, int64_t splits) {
-  const char* name = "decode_attn";
-  const int64_t D = head_dim;
+namespace {
+
+// decode_attn (Q = 1) and decode_attn_multi: qkv holds Q tokens for each of rows.numel() sequences, lens
+// one entry per token.  Q = 1 runs the one-token kernel, Q > 1 the tile of decode::q_tile(G) tokens.
+at::Tensor decode_launch(const char* name, const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                         const at::Tensor& rows, const at::Tensor& lens, int64_t Q, int64_t nq, int64_t nkv, int64_t D,
+                         double scale, int64_t max_len, int64_t window, int64_t splits) {
   check_qkv(qkv, nq, nkv, D, name);
   const int64_t G = nq / nkv;
   DTG_CHECK(decode::group_ok(G), name, ": query heads per kv head must be one of 1, 2, 3, 4, 7, 8, 16");
   check_cache(k_cache, v_cache, nkv, D, name);
-  const int64_t B = qkv.size(0), S_max = k_cache.size(2);
-  check_index(rows, B, name, "rows");
-  check_index(lens, B, name, "lens");
+  const int64_t T = qkv.size(0), S_max = k_cache.size(2);
+  DTG_CHECK(Q >= 1 && Q < (int64_t(1) << 20) && T % Q == 0, name, ": q_len must be >= 1 and divide the rows of qkv");
+  const int64_t B = T / Q;
+  check_index(rows, B, name, "rows", Q == 1 ? "token" : "sequence");
+  check_index(lens, T, name, "lens");
   DTG_CHECK(max_len >= 0 && max_len <= S_max, name, ": max_len must lie in [0, S_max]");
   DTG_CHECK(window >= 0 && splits >= 0, name, ": window and splits must not be negative");
   const c10::DeviceGuard dg(qkv.device());
-  auto out = at::empty({B, nq * D}, qkv.options());
-  if (B == 0) return out;
+  auto out = at::empty({T, nq * D}, qkv.options());
+  if (T == 0) return out;
   const int cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
-  const decode::Plan p = decode::plan({B, (int)nkv, (int)G, (int)D, max_len, window, cus, (int)splits});
+  const decode::Plan p = decode::plan_multi({B, (int)nkv, (int)G, (int)D, max_len, window, cus, (int)splits}, (int)Q);
   const int64_t nwg = (int64_t)p.grid.x * p.grid.y * p.grid.z;
   DTG_CHECK(nwg < (int64_t(1) << 31), name, ": too many workgroups");
   float *ws_o = nullptr, *ws_ml = nullptr;
   at::Tensor ws;
-  if (p.splits > 1) {  // [B nkv splits G D] outputs, then [B nkv splits G 2] max | sum
+  if (p.splits > 1) {  // [T nkv splits G D] outputs, then [T nkv splits G 2] max | sum
     ws = at::empty({(int64_t)(p.ws_bytes / sizeof(float))}, qkv.options().dtype(at::kFloat));
     ws_o = ws.data_ptr<float>();
-    ws_ml = ws_o + B * nkv * p.splits * G * D;
+    ws_ml = ws_o + T * nkv * p.splits * G * D;
   }
-#define DTG_DECODE_LAUNCH(D_, G_)                                                                                   \
-  decode_attn_kernel<D_, G_><<<(unsigned)nwg, decode::kThreads, 0, stream()>>>(                                     \
+#define DTG_DECODE_LAUNCH(D_, G_, QT_)                                                                              \
+  decode_attn_kernel<D_, G_, QT_><<<(unsigned)nwg, decode::kThreads, 0, stream()>>>(                                \
       bf16_ptr(qkv), qkv.stride(0), bf16_ptr(k_cache), bf16_ptr(v_cache), rows.data_ptr<int32_t>(),                 \
       lens.data_ptr<int32_t>(), ws_o, ws_ml, bf16_mut(out), (int)nkv, p.splits, p.chunk, window, k_cache.size(0), \
-      S_max, (float)scale)
-#define DTG_DECODE_G(D_)                                  \
-  switch (G) {                                            \
-    case 1: DTG_DECODE_LAUNCH(D_, 1); break;              \
-    case 2: DTG_DECODE_LAUNCH(D_, 2); break;              \
-    case 3: DTG_DECODE_LAUNCH(D_, 3); break;              \
-    case 4: DTG_DECODE_LAUNCH(D_, 4); break;              \
-    case 7: DTG_DECODE_LAUNCH(D_, 7); break;              \
-    case 8: DTG_DECODE_LAUNCH(D_, 8); break;              \
-    default: DTG_DECODE_LAUNCH(D_, 16); break;            \
+      S_max, (float)scale, (int)Q)
+#define DTG_DECODE_GQ(D_, G_, QT_)                \
+  if (Q == 1) {                                   \
+    DTG_DECODE_LAUNCH(D_, G_, 1);                 \
+  } else {                                        \
+    static_assert(QT_ == decode::q_tile(G_), "q tile"); \
+    DTG_DECODE_LAUNCH(D_, G_, QT_);               \
+  }                                               \
+  break
+#define DTG_DECODE_G(D_)                          \
+  switch (G) {                                    \
+    case 1: DTG_DECODE_GQ(D_, 1, 8);              \
+    case 2: DTG_DECODE_GQ(D_, 2, 8);              \
+    case 3: DTG_DECODE_GQ(D_, 3, 4);              \
+    case 4: DTG_DECODE_GQ(D_, 4, 4);              \
+    case 7: DTG_DECODE_GQ(D_, 7, 2);              \
+    case 8: DTG_DECODE_GQ(D_, 8, 2);              \
+    default: DTG_DECODE_GQ(D_, 16, 1);            \
   }
   DTG_HD_DISPATCH(D, DTG_DECODE_G(HD))
 #undef DTG_DECODE_G
+#undef DTG_DECODE_GQ
 #undef DTG_DECODE_LAUNCH
   DTG_LAUNCH_CHECK();
   if (p.splits > 1) {
-    DTG_HD_DISPATCH(D, decode_combine_kernel<HD><<<(unsigned)(B * nkv), decode::kThreads, 0, stream()>>>(
+    DTG_HD_DISPATCH(D, decode_combine_kernel<HD><<<(unsigned)(T * nkv), decode::kThreads, 0, stream()>>>(
                            ws_o, ws_ml, bf16_mut(out), (int)G, p.splits));
     DTG_LAUNCH_CHECK();
   }
   return out;
 }
 
+}  // namespace
+
+at::Tensor decode_attn(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                       const at::Tensor& rows, const at::Tensor& lens, int64_t nq, int64_t nkv, int64_t head_dim,
+                       double scale, int64_t max_len, int64_t window, int64_t splits) {
+  return decode_launch("decode_attn", qkv, k_cache, v_cache, rows, lens, 1, nq, nkv, head_dim, scale, max_len, window,
+                       splits);
+}
+
+at::Tensor decode_attn_multi(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                             const at::Tensor& rows, const at::Tensor& lens, int64_t q_len, int64_t nq, int64_t nkv,
+                             int64_t head_dim, double scale, int64_t max_len, int64_t window, int64_t splits) {
+  return decode_launch("decode_attn_multi", qkv, k_cache, v_cache, rows, lens, q_len, nq, nkv, head_dim, scale, max_len,
+                       window, splits);
+}
+
 TORCH_LIBRARY_IMPL(dtg, CUDA, m) {
   m.impl("kv_cache_append_", &kv_cache_append_);
   m.impl("decode_attn", &decode_attn);
+  m.impl("decode_attn_multi", &decode_attn_multi);
 }
 
 }  // namespace dtg

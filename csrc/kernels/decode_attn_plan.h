@@ -76,5 +76,28 @@ inline Plan plan(const Call& c) {
   return p;
 }
 
+// decode_attn_multi: Q new tokens per sequence (speculative verification).  A workgroup serves a tile of
+// q_tile(G) consecutive tokens of one sequence times the G query heads of its kv head, so a K / V piece
+// is used G * q_tile(G) times.  16 (token, head) pairs per lane is what the G = 16 form of the
+// one-token kernel already keeps in registers (16 x 8 q and 16 x 8 accumulators, 1 wave per SIMD).
+constexpr int kMaxPairs = 16;
+constexpr int q_tile(int G) {
+  int qt = 1;
+  while (qt < 8 && G * qt * 2 <= kMaxPairs) qt *= 2;
+  return qt;
+}
+
+// Splits and chunk are plan(c)'s: c.B stays the number of sequences, so a token's keys are divided
+// exactly as decode_attn divides them for that token alone with the same max_len and splits (the
+// bitwise contract of decode_attn_multi).  Q only adds a query-tile dimension to the grid, folded into
+// grid.z = sequence * ceil(Q / q_tile) + tile, and multiplies the partials, which are indexed with the
+// token in the place of the sequence.
+inline Plan plan_multi(const Call& c, int Q) {
+  Plan p = plan(c);
+  p.grid.z = (unsigned)(c.B * ceil_div(Q, q_tile(c.G)));
+  p.ws_bytes *= (size_t)Q;
+  return p;
+}
+
 }  // namespace decode
 }  // namespace dtg

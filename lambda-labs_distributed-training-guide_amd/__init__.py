@@ -22,4 +22,8 @@ def __getattr__(name):  # `from dtg import generate` without importing torch at 
         from .models.quantized import Fp8DecodeWeights
 
         return Fp8DecodeWeights
+    if name == "Speculative":
+        from .models.speculative import Speculative
+
+        return Speculative
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

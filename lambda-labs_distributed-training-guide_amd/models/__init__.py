@@ -3,8 +3,9 @@ import torch
 
 from .config import GPT2Config, LlamaConfig, available_configs, resolve_config
 from .decode_graph import GraphedDecode
-from .generation import KVCache, decode_bucket, decode_step, generate, prefill
+from .generation import KVCache, decode_bucket, decode_step, extend_step, generate, prefill
 from .gpt2 import GPT2LMHeadModel
+from .speculative import NgramDrafter, Speculative
 from .quantized import Fp8DecodeWeights
 from .llama import CausalLMOutput, LlamaForCausalLM, count_valid_labels
 
@@ -63,4 +64,4 @@ def resize_token_embeddings(model, new_vocab: int):
 __all__ = ["GPT2Config", "LlamaConfig", "available_configs", "resolve_config", "GPT2LMHeadModel",
            "LlamaForCausalLM", "CausalLMOutput", "count_valid_labels", "build_model", "resize_token_embeddings",
            "mean_resized_rows", "KVCache", "prefill", "decode_step", "generate", "decode_bucket",
-           "GraphedDecode", "Fp8DecodeWeights"]
+           "GraphedDecode", "Fp8DecodeWeights", "extend_step", "Speculative", "NgramDrafter"]

@@ -140,12 +140,14 @@ def _run_layers(model, x, append_and_attend, linear="blas", fp8=None):
     return x, res
 
 
-def _append(attn, qkv, cache, i, cos, sin, pos, rows, pos_max):
+def _append(attn, qkv, cache, i, cos, sin, pos, rows, pos_max, rope_pos=None):
     """RoPE (after the per-head norm for Qwen3, whose fused pass ropes itself) and the cache write.
-    `pos_max`: the host's largest position of the call, checked by the op (rows were checked by _rows)."""
+    `pos_max`: the host's largest position of the call, checked by the op (rows were checked by _rows).
+    `rope_pos`: in-table positions for Qwen3's pass where `pos` marks tokens to skip with -1 (extend_step);
+    the append itself skips them."""
     if attn.qk_norm:
         qkv = ops.qk_norm_rope(qkv, attn.q_norm.weight, attn.k_norm.weight, attn.eps, attn.nq, attn.nkv, attn.d,
-                               cos, sin, pos)
+                               cos, sin, pos if rope_pos is None else rope_pos)
         return ops.kv_cache_append(qkv, cache.k[i], cache.v[i], pos, rows, attn.nq, attn.nkv, attn.d, pos_max=pos_max)
     return ops.kv_cache_append(qkv, cache.k[i], cache.v[i], pos, rows, attn.nq, attn.nkv, attn.d, cos, sin,
                                pos_max=pos_max)
@@ -253,6 +255,59 @@ def decode_step(model, tokens: torch.Tensor, cache: KVCache, rows: Optional[Sequ
     return logits
 
 
+@torch.no_grad()
+def extend_step(model, tokens: torch.Tensor, q_valid: torch.Tensor, cache: KVCache, rows: Optional[Sequence[int]] = None,
+                linear: str = "blas", plan_len: Optional[int] = None, fp8=None):
+    """Up to Q new tokens per active sequence in one pass (`tokens` [n, Q] ids, `q_valid` [n]: how many of a
+    row's Q are real): the verify pass of speculative decoding.  Token t < q_valid[b] of row b is appended at
+    position cache.lens[b] + t and attends the keys up to and including its own (`ops.decode_attention_multi`
+    with lens = pos + 1); a token t >= q_valid[b] is written nowhere (pos = -1) and attends nothing (len = 0), its
+    logits mean nothing.  Returns the logits [n * Q, V], row b * Q + t = the prediction after token t.
+
+    Built from device tensors only (`q_valid` is not read on the host).  Does NOT advance cache.lens or
+    cache.max_len: the caller does, by the number of tokens it accepts; what it rejects stays past lens and is
+    overwritten later.  `plan_len` as in `decode_step` (default: cache.max_len + Q, capped at S_max); it must
+    cover the largest length the pass attends.  linear="skinny" / "skinny-fp8" run all n * Q rows in one
+    skinny GEMM, so n * Q may not exceed its row limit."""
+    _check_model(model)
+    dev = cache.lens.device
+    if tokens.dim() != 2 or tokens.shape[1] < 1:
+        raise ValueError(f"extend_step: tokens must be [n, Q] with Q >= 1, got {tuple(tokens.shape)}")
+    n, Q = tokens.shape
+    if q_valid.dim() != 1 or q_valid.numel() != n:
+        raise ValueError(f"extend_step: q_valid must be [{n}], got {tuple(q_valid.shape)}")
+    _check_linear(linear)
+    if linear != "blas" and n * Q > SKINNY_MAX_M:
+        raise ValueError(f'extend_step: linear="{linear}" takes at most {SKINNY_MAX_M} rows per pass, got '
+                         f"{n} sequences x {Q} tokens = {n * Q}")
+    fp8 = _check_fp8(model, linear, fp8)
+    if cache.max_len + 1 > cache.s_max:
+        raise ValueError(f"extend_step: the cache is full (S_max = {cache.s_max})")
+    if plan_len is None:
+        plan_len = min(cache.max_len + Q, cache.s_max)
+    plan_len = int(plan_len)
+    if not cache.max_len + 1 <= plan_len <= cache.s_max:
+        raise ValueError(f"extend_step: plan_len {plan_len} outside [cache.max_len + 1 = {cache.max_len + 1}, "
+                         f"S_max = {cache.s_max}]")
+    rows_t = _rows(cache, n, rows, dev)
+    t = torch.arange(Q, device=dev)
+    base = cache.lens[rows_t.long()].long()
+    live = t[None] < q_valid.to(dev)[:, None]
+    pos = torch.where(live, base[:, None] + t[None], torch.full((), -1, dtype=torch.long, device=dev)).reshape(-1)
+    lens = (pos + 1).to(torch.int32)
+    rope_pos = pos.clamp(0, cache.s_max - 1)
+    tok_rows = rows_t.repeat_interleave(Q)
+    cos, sin = model._rope_tables(cache.s_max, dev)
+
+    def attend(i, attn, qkv):
+        qkv = _append(attn, qkv, cache, i, cos, sin, pos, tok_rows, plan_len - 1, rope_pos)
+        return ops.decode_attention_multi(qkv, cache.k[i], cache.v[i], rows_t, lens, Q, attn.nq, attn.nkv, attn.d,
+                                          plan_len, window=attn.window)
+
+    x, res = _run_layers(model, ops.embedding(tokens.reshape(-1).to(dev), model.embed_tokens.weight), attend, linear, fp8)
+    return _last_logits(model, x, res, linear, fp8)
+
+
 def decode_bucket(length: int, s_max: int) -> int:
     """The length bucket a captured decode step is planned for: the smallest of 256, 512, 1024, ... that is
     >= `length`, capped at `s_max`.  256 is the decode plan's smallest chunk (decode::kMinChunk): below it
@@ -299,7 +354,7 @@ def _fused_params(n, **given):
 def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              top_p: float = 1.0, eos_token_id: Optional[int] = None, seed: int = 0, s_max: Optional[int] = None,
              min_p: float = 0.0, sampler: str = "torch", linear: str = "blas", decode="eager",
-             bucketed: bool = False, fp8=None) -> List[torch.Tensor]:
+             bucketed: bool = False, fp8=None, speculate=None) -> List[torch.Tensor]:
     """Continue every prompt by up to `max_new_tokens` ids; returns the new ids of each sequence (1-D
     int64 tensors on the CPU), ending with `eos_token_id` where the sequence produced it.
 
@@ -323,7 +378,13 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     sampler="fused", whose draw counter lives on the device.  `decode` may also be a `GraphedDecode`
     built for this model, batch size and `s_max`: its graphs and cache are reused.  decode="eager" with
     `bucketed=True` runs the eager loop with the launch plans of the captured one (plan_len = the
-    bucket): with linear="skinny" the two loops return the same ids bit for bit."""
+    bucket): with linear="skinny" the two loops return the same ids bit for bit.
+
+    `speculate` (a `Speculative`, models/speculative.py; None leaves everything above as it is): speculative
+    decoding with exact-match verification.  Every step runs the last accepted id and up to k - 1 drafted ids
+    of each row through one `extend_step` and keeps the drafted ids that equal the model's own id of their
+    position.  Eager only; sampling needs sampler="fused".  With linear="skinny" / "skinny-fp8" (at most
+    SKINNY_MAX_M rows: prompts x k) the ids are those of the plain loop planned for the same length, bit for bit."""
     _check_model(model)
     prompts = [p.reshape(-1) for p in prompts]
     if not prompts or min(p.numel() for p in prompts) < 1:
@@ -337,6 +398,10 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     if not graphed and decode not in ("eager", "graph"):
         raise ValueError(f"generate: decode must be 'eager', 'graph' or a GraphedDecode, got {decode!r}")
     graphed = graphed or decode == "graph"
+    if speculate is not None:
+        from .speculative import check_speculate
+
+        check_speculate(speculate, len(prompts), linear, graphed, sampler, temperature)
     if graphed:
         sampled = any(float(t) > 0.0 for t in (temperature.tolist() if isinstance(temperature, torch.Tensor) else
                                                temperature if isinstance(temperature, (list, tuple)) else [temperature]))
@@ -376,6 +441,10 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
             raise ValueError("generate: the GraphedDecode was captured with other fp8 weights")
         return gd.run(prompts, max_new_tokens, fused, seed, eos_token_id, s_max=s_max, linear=linear)
     fp8 = _check_fp8(model, linear, fp8, build=True)
+    if speculate is not None:
+        from .speculative import speculative_loop
+
+        return speculative_loop(model, prompts, max_new_tokens, speculate, fused, seed, eos_token_id, s_max, linear, fp8)
     gen = None
     if fused is not None:
         fused = {k: torch.tensor(v, dtype=torch.int32 if k == "top_k" else torch.float32, device=dev)

@@ -20,6 +20,7 @@ from .functional import (  # noqa: E402
     attention,
     check_sample_scalar,
     decode_attention,
+    decode_attention_multi,
     dropout_add_layer_norm,
     embedding,
     fused_linear_cross_entropy,
@@ -63,5 +64,5 @@ __all__ = [
     "add_rms_norm", "attention", "rope", "embedding", "fused_linear_cross_entropy", "linear", "rms_norm",
     "rope_tables", "swiglu", "swiglu_mlp", "vocab_parallel_fused_linear_cross_entropy", "route_param_grad", "adamw_step",
     "fa_tuning", "layer_norm", "dropout_add_layer_norm", "gelu_mlp", "qk_norm_rope", "kv_cache_append", "decode_attention",
-    "sample_logits", "skinny_linear", "skinny_linear_fp8", "quantize_fp8_rows",
+    "sample_logits", "skinny_linear", "skinny_linear_fp8", "quantize_fp8_rows", "decode_attention_multi",
 ]

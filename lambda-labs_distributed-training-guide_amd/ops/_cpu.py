@@ -144,6 +144,15 @@ def decode_attn(qkv, k_cache, v_cache, rows, lens, nq, nkv, head_dim, scale, max
     return out
 
 
+def decode_attn_multi(qkv, k_cache, v_cache, rows, lens, q_len, nq, nkv, head_dim, scale, max_len, window, splits):
+    """q_len tokens per sequence, token (b, t) = row b * q_len + t of qkv and lens, against cache row rows[b]:
+    decode_attn's loop over the tokens."""
+    if q_len < 1 or qkv.shape[0] % q_len or rows.numel() * q_len != qkv.shape[0] or lens.numel() != qkv.shape[0]:
+        raise RuntimeError("dtg: decode_attn_multi: qkv and lens need q_len >= 1 rows per entry of rows")
+    return decode_attn(qkv, k_cache, v_cache, rows.repeat_interleave(q_len), lens, nq, nkv, head_dim, scale, max_len,
+                       window, splits)
+
+
 def swiglu_fwd(gu):
     inter = gu.shape[1] // 2
     g, u = gu[:, :inter].float(), gu[:, inter:].float()
@@ -835,6 +844,6 @@ for _name, _fn in list(globals().items()):
         "flash_attn_varlen_bwd", "flash_attn_fwd_drop", "flash_attn_bwd_drop", "flash_attn_bwd_qkv_drop", "philox_rng",
         "flash_attn_bwd_qkv_rope", "flash_attn_tuning", "layernorm_fwd", "dropout_add_layernorm_fwd", "layernorm_bwd",
         "gelu_fwd", "gelu_bwd", "gelu_bwd_t", "qk_norm_rope_fwd_", "qk_norm_rope_bwd_", "kv_cache_append_", "decode_attn",
-        "sample_logits", "skinny_linear", "skinny_linear_fp8",
+        "sample_logits", "skinny_linear", "skinny_linear_fp8", "decode_attn_multi",
     ):
         LIB.impl(_name, _fn, "CPU")

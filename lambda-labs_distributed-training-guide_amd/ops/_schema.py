@@ -44,6 +44,13 @@ _DEFS = [
     # max_len a host upper bound of lens (launch plan only), splits = 0 takes the plan's split count
     "decode_attn(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor rows, Tensor lens, int nq, int nkv, int head_dim, "
     "float scale, int max_len, int window=0, int splits=0) -> Tensor",
+    # q_len new tokens per sequence (speculative verification): qkv [B * q_len, ...] sequence-major, rows int32 [B],
+    # lens int32 [B * q_len], one attended length per token; token (b, t) attends keys [max(0, len - window), len)
+    # of cache row rows[b] (len <= 0 or a bad row: a row of zeros).  Causality among the new tokens is the
+    # caller's (it passes pos + 1).  At window 0 a token's output row is bit for bit decode_attn's for that token
+    # alone with the same max_len and splits.  The keys between the ranges of one sequence's tokens are read too.
+    "decode_attn_multi(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor rows, Tensor lens, int q_len, int nq, "
+    "int nkv, int head_dim, float scale, int max_len, int window, int splits) -> Tensor",
     # fused top-k / top-p / min-p sampling (csrc/kernels/sample.hip): logits [n, V] bf16 / f32 with unit
     # inner stride; params f32 [n, 3] = temperature, top_p, min_p; top_k int32 [n]; rng int64 [n, 3] =
     # seed, stream, step of the row's Philox draw; u f32 [n] in [0, 1) replaces that draw.  Returns

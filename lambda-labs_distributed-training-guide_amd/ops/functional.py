@@ -606,6 +606,43 @@ def decode_attention(qkv, k_cache, v_cache, rows, lens, nq, nkv, head_dim, max_l
     return torch.einsum("bhgs,bhsd->bhgd", p, v).reshape(B, nq * d).to(qkv.dtype)
 
 
+@torch.no_grad()
+def decode_attention_multi(qkv, k_cache, v_cache, rows, lens, q_len, nq, nkv, head_dim, max_len, scale=None, window=0,
+                           splits=0):
+    """Attention of `q_len` new tokens per sequence against its KV-cache row -> [B * q_len, nq * d]: the verify
+    pass of speculative decoding.
+
+    `qkv` is [B * q_len, ...] sequence-major (token t of sequence b is row b * q_len + t), `rows` [B] the cache
+    rows, `lens` [B * q_len] one attended length per token: token (b, t) attends keys
+    [max(0, len - window), len) of cache row rows[b]; len <= 0 or a row outside the cache gives a row of zeros.
+    Causality among the new tokens is the caller's: it appends them first and passes pos + 1.  `max_len` and
+    `splits` as in `decode_attention`.  At window 0 the kernel's output row of a token equals, bit for bit,
+    `decode_attention` of that token alone with the same `max_len` and `splits`."""
+    q_len, nq, nkv, d = int(q_len), int(nq), int(nkv), int(head_dim)
+    if q_len < 1 or qkv.dim() != 2 or qkv.shape[0] % q_len:
+        raise ValueError(f"decode_attention_multi: q_len ({q_len}) must be >= 1 and divide the rows of qkv "
+                         f"{tuple(qkv.shape)}")
+    _check_cache_args("decode_attention_multi", qkv, k_cache, v_cache, nq, nkv, d, {"lens": lens})
+    B = qkv.shape[0] // q_len
+    if rows.dim() != 1 or rows.numel() != B or rows.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"decode_attention_multi: rows must be an integer tensor [{B}] (one cache row per sequence), "
+                         f"got {rows.dtype} {tuple(rows.shape)}")
+    max_len, window, splits = int(max_len), int(window or 0), int(splits)
+    if not 0 <= max_len <= k_cache.shape[2]:
+        raise ValueError(f"decode_attention_multi: max_len {max_len} outside [0, S_max = {k_cache.shape[2]}]")
+    if window < 0 or splits < 0:
+        raise ValueError("decode_attention_multi: window and splits must not be negative")
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    if _decode_kernels(qkv, nq, nkv, d):
+        return ops.decode_attn_multi(qkv, k_cache, v_cache, rows.to(torch.int32).contiguous(),
+                                     lens.to(torch.int32).contiguous(), q_len, nq, nkv, d, float(scale), max_len, window,
+                                     splits)
+    # decode_attention's composition (the same rule sends it there), one query row per token: masked slots zeroed
+    return decode_attention(qkv, k_cache, v_cache, rows.repeat_interleave(q_len), lens, nq, nkv, d, max_len, scale, window,
+                            splits)
+
+
 # --------------------------------------------------------------------------------------------
 # Sampling: fused top-k / top-p / min-p with a per-sequence Philox draw (csrc/kernels/sample.hip)
 # --------------------------------------------------------------------------------------------

@@ -67,6 +67,11 @@ def main(argv=None):
     ap.add_argument("--decode", choices=("eager", "graph"), default="eager",
                     help="graph: capture the decode step into one HIP graph per length bucket and replay it (GPU; "
                     "sampling then needs --sampler fused)")
+    ap.add_argument("--speculate", choices=("ngram",), default=None,
+                    help="speculative decoding with exact-match verification: the prompt-lookup drafter (eager decode; "
+                    "sampling needs --sampler fused); prints the acceptance stats")
+    ap.add_argument("--draft-tokens", type=int, default=4, metavar="K",
+                    help="tokens per verify pass and prompt: the last accepted id plus K - 1 drafted ids")
     ap.add_argument("--eos-token-id", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default=None, help="default: cuda if available, else cpu")
@@ -118,12 +123,21 @@ def main(argv=None):
         if dev.type == "cuda":
             torch.cuda.synchronize()
 
+    spec = None
+    if a.speculate is not None:
+        try:
+            spec = dtg.Speculative(a.speculate, k=a.draft_tokens)
+        except ValueError as e:
+            raise SystemExit(f"--draft-tokens: {e}")
     sync()
     t0 = time.perf_counter()
     out = dtg.generate(model, prompts, a.max_new_tokens, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p,
-                       eos_token_id=eos, seed=a.seed, min_p=a.min_p, sampler=a.sampler, linear=a.linear, decode=a.decode)
+                       eos_token_id=eos, seed=a.seed, min_p=a.min_p, sampler=a.sampler, linear=a.linear, decode=a.decode,
+                       speculate=spec)
     sync()
     dt = time.perf_counter() - t0
+    if spec is not None:
+        print(json.dumps({"speculate": a.speculate, "draft_tokens": spec.k, **spec.stats}))
     for i, ids in enumerate(out):
         print(f"ids[{i}]: {','.join(str(int(t)) for t in ids)}")
         if tok is not None:
