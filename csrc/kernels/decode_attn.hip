@@ -33,6 +33,23 @@
 // sequence, so decode_combine_kernel serves unchanged.  At window 0 a token's output row is, bit for bit,
 // decode_attn's for that token alone with the same max_len and splits.  Keys past the largest length of
 // a tile's tokens are never loaded; keys between its tokens' ranges are (they score -inf).
+//
+// Cache formats (the template parameter Fmt of the append and of the attention, the way skinny_gemm.hip
+// takes a weight format).  Bf16Cache: everything above.  E4m3Cache (kv_cache_append_fp8_, decode_attn_fp8):
+// K / V are OCP e4m3fn bytes in the same [rows_max, nkv, S_max, D] layout, with one f32 scale per key vector,
+// [rows_max, nkv, S_max], for K and for V.  The scale is the power of two that puts the vector's largest
+// magnitude into (224, 448] (1 for an all-zero vector, floored at 2^-100): ops.quantize_fp8_rows(pow2=True)
+// of the D-vector, bit for bit.  The append takes amax over the head's D/16 lanes with a sub-wave butterfly
+// (all lanes of a head belong to one token and return together), builds the scale from amax's exponent bits,
+// divides exactly, clamps to +-448 (a NaN stays NaN: code 0x7f), converts with v_cvt_pk_fp8_f32 (round to
+// nearest even), stores two 8-byte pieces of codes per thread and the scale from the group's first lane,
+// and writes the DEQUANTISED k / v back into qkv, so a prefill that attends qkv sees what the cache holds.
+// code * scale is exactly a bf16 value: the FP8 cache is exactly some bf16 cache.  The attention keeps the
+// lane map (a lane loads 8 bytes per key and tensor instead of 16), widens with v_cvt_pk_f32_fp8 and
+// multiplies by the key's scale (exact) before first use; from there on the arithmetic is the bf16
+// kernel's, expression for expression, so decode_attn_fp8(codes, scales) equals decode_attn(dequantised
+// cache) bit for bit (for scales whose products stay in the normal f32 range).  A key's scale is loaded
+// only where the key is.  Plan, partial workspace and combine kernel are shared.
 #include "decode_attn_plan.h"
 #include "rope_common.h"
 
@@ -45,9 +62,82 @@ namespace {
 // exp(m - m_new) of a running max that may still be -inf (nothing seen): weight 0, never NaN
 __device__ __forceinline__ float rescale(float m, float m_new) { return m == -INFINITY ? 0.f : __expf(m - m_new); }
 
-template <int D, bool ROPE>
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int kFp8MinScaleExp = -100;  // ops.FP8_MIN_SCALE_EXP
+
+struct NoScale {};  // an empty kernel argument: the bf16 kernels carry no scale pointers
+
+// A cache format: the element type, the scale arguments of the kernels, and a lane's 8 dims of one key
+// (Piece) with its load and its widening to f32.
+struct Bf16Cache {
+  static constexpr bool kFp8 = false;
+  using Elem = uint16_t;
+  using Scale = NoScale;     // read by the attention
+  using ScaleOut = NoScale;  // written by the append
+  using Piece = u16x8;
+  static __device__ __forceinline__ Scale at(Scale s, int64_t) { return s; }
+  static __device__ __forceinline__ Piece zero() { return u16x8{0, 0, 0, 0, 0, 0, 0, 0}; }
+  static __device__ __forceinline__ Piece load(const Elem* p, Scale, int64_t) {
+    return *reinterpret_cast<const u16x8*>(p);
+  }
+  static __device__ __forceinline__ void widen(const Piece& v, float* out) { widen8(v, out); }
+};
+
+struct E4m3Cache {
+  static constexpr bool kFp8 = true;
+  using Elem = uint8_t;
+  using Scale = const float*;
+  using ScaleOut = float*;
+  struct Piece {
+    uint2 v;
+    float s;
+  };
+  static __device__ __forceinline__ Scale at(Scale s, int64_t off) { return s + off; }
+  static __device__ __forceinline__ Piece zero() { return Piece{make_uint2(0u, 0u), 1.f}; }
+  // `s` points at the scales of the kv head's row, j is the key
+  static __device__ __forceinline__ Piece load(const Elem* p, Scale s, int64_t j) {
+    return Piece{*reinterpret_cast<const uint2*>(p), s[j]};
+  }
+  // eight e4m3 bytes (memory order = ascending byte) through v_cvt_pk_f32_fp8
+  static __device__ __forceinline__ void codes(uint2 v, float* out) {
+    const uint32_t w[2] = {v.x, v.y};
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+      const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[d], false);
+      const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[d], true);
+      out[4 * d] = lo[0];
+      out[4 * d + 1] = lo[1];
+      out[4 * d + 2] = hi[0];
+      out[4 * d + 3] = hi[1];
+    }
+  }
+  // code * 2^k is exact: the values are those of the bf16 cache this one stands for
+  static __device__ __forceinline__ void widen(const Piece& p, float* out) {
+    codes(p.v, out);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) out[i] *= p.s;
+  }
+};
+
+// The e4m3 codes of 8 values already divided by the scale: clamped to +-448 by comparisons, which a NaN
+// passes (it becomes the code 0x7f), rounded to nearest even by v_cvt_pk_fp8_f32.
+__device__ __forceinline__ uint2 e4m3_pack8(const float* x) {
+  float c[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) c[i] = x[i] > 448.f ? 448.f : (x[i] < -448.f ? -448.f : x[i]);
+  int lo = 0, hi = 0;
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], lo, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], lo, true);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(c[4], c[5], hi, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(c[6], c[7], hi, true);
+  return make_uint2((uint32_t)lo, (uint32_t)hi);
+}
+
+template <class Fmt, int D, bool ROPE>
 __global__ __launch_bounds__(256) void kv_append_kernel(
-    uint16_t* __restrict__ qkv, int64_t row_stride, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc,
+    uint16_t* __restrict__ qkv, int64_t row_stride, typename Fmt::Elem* __restrict__ kc,
+    typename Fmt::Elem* __restrict__ vc, typename Fmt::ScaleOut ksc, typename Fmt::ScaleOut vsc,
     const float* __restrict__ cos_t, const float* __restrict__ sin_t, int64_t max_pos,
     const int64_t* __restrict__ pos, const int32_t* __restrict__ rows, int nq, int nkv, int64_t T, int64_t rows_max,
     int64_t S_max) {
@@ -74,15 +164,55 @@ __global__ __launch_bounds__(256) void kv_append_kernel(
       b1[j] = f2bf(x1[j]);
       b2[j] = f2bf(x2[j]);
     }
-    *reinterpret_cast<u16x8*>(base) = b1;
-    *reinterpret_cast<u16x8*>(base + HALF) = b2;
+    if (!Fmt::kFp8 || it.head < nq) {  // the FP8 form stores a k head once, dequantised, below
+      *reinterpret_cast<u16x8*>(base) = b1;
+      *reinterpret_cast<u16x8*>(base + HALF) = b2;
+    }
   }
   if (it.head >= nq) {
     const bool is_k = it.head < nq + nkv;
     const int kvh = is_k ? it.head - nq : it.head - nq - nkv;
-    uint16_t* dst = (is_k ? kc : vc) + ((r * nkv + kvh) * S_max + p) * D + it.grp * 8;
-    *reinterpret_cast<u16x8*>(dst) = b1;
-    *reinterpret_cast<u16x8*>(dst + HALF) = b2;
+    const int64_t slot = (r * nkv + kvh) * S_max + p;
+    if constexpr (Fmt::kFp8) {
+      // The head's D/16 lanes are consecutive, aligned, and all here: they share the token, so they passed
+      // the early returns together, and the head, so they took this branch together.
+      float x1[8], x2[8];
+      widen8(b1, x1);
+      widen8(b2, x2);
+      float amax = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fmaxf(fabsf(x1[j]), fabsf(x2[j])));
+#pragma unroll
+      for (int o = D / 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, kWave));
+      // amax = (1 + f) 2^(E - 127): a significand up to 1.75 (= 448 / 256) goes to [256, 448] with the scale
+      // 2^(E - 135), a larger one to (224, 256) with 2^(E - 134); subnormals end at the floor
+      const uint32_t ab = __float_as_uint(amax);
+      const int E = (int)(ab >> 23);
+      int k = E - ((ab & 0x7fffffu) <= 0x600000u ? 135 : 134);
+      k = k < kFp8MinScaleExp ? kFp8MinScaleExp : k;
+      if (amax == 0.f) k = 0;
+      const float sc = __uint_as_float((uint32_t)(k + 127) << 23);
+      const float inv = __uint_as_float((uint32_t)(127 - k) << 23);  // exact: the product is the quotient
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        x1[j] *= inv;
+        x2[j] *= inv;
+      }
+      const uint2 c1 = e4m3_pack8(x1), c2 = e4m3_pack8(x2);
+      uint8_t* dst = (is_k ? kc : vc) + slot * D + it.grp * 8;
+      *reinterpret_cast<uint2*>(dst) = c1;
+      *reinterpret_cast<uint2*>(dst + HALF) = c2;
+      if (it.grp == 0) (is_k ? ksc : vsc)[slot] = sc;
+      // what the cache now holds goes back into qkv, for the prefill's attention
+      E4m3Cache::widen(E4m3Cache::Piece{c1, sc}, x1);
+      E4m3Cache::widen(E4m3Cache::Piece{c2, sc}, x2);
+      store8(base, x1);
+      store8(base + HALF, x2);
+    } else {
+      uint16_t* dst = (is_k ? kc : vc) + slot * D + it.grp * 8;
+      *reinterpret_cast<u16x8*>(dst) = b1;
+      *reinterpret_cast<u16x8*>(dst + HALF) = b2;
+    }
   }
 }
 
@@ -93,12 +223,13 @@ __global__ __launch_bounds__(256) void kv_append_kernel(
 // tokens that hold keys in this split (all equal split * chunk without a window, so key j sits in the
 // same lane whatever the query) and runs to their largest k1; a key outside a token's own [k0, k1)
 // scores -inf for it, which leaves its (m, l, acc) as they were: alpha = exp(m - m) = 1, p = 0.
-template <int D, int G, int QT>
+template <class Fmt, int D, int G, int QT>
 __global__ __launch_bounds__(decode::kThreads) void decode_attn_kernel(
-    const uint16_t* __restrict__ qkv, int64_t q_stride, const uint16_t* __restrict__ kc,
-    const uint16_t* __restrict__ vc, const int32_t* __restrict__ rows, const int32_t* __restrict__ lens,
+    const uint16_t* __restrict__ qkv, int64_t q_stride, const typename Fmt::Elem* __restrict__ kc,
+    const typename Fmt::Elem* __restrict__ vc, const int32_t* __restrict__ rows, const int32_t* __restrict__ lens,
     float* __restrict__ ws_o, float* __restrict__ ws_ml, uint16_t* __restrict__ out, int nkv, int splits,
-    int64_t chunk, int64_t window, int64_t rows_max, int64_t S_max, float scale, int Q) {
+    int64_t chunk, int64_t window, int64_t rows_max, int64_t S_max, float scale, int Q, typename Fmt::Scale ksc,
+    typename Fmt::Scale vsc) {
   // Every multiply-add below is written out (fmaf, or a product and a sum that stay apart): left to the
   // compiler, which products fuse with which sums differed from element to element and from one
   // instantiation to the next, and the bits of the QT > 1 forms would not be those of QT = 1.
@@ -159,10 +290,12 @@ __global__ __launch_bounds__(decode::kThreads) void decode_attn_kernel(
   }
 
   const int64_t head_off = ((k1 > k0 ? row : 0) * nkv + h) * S_max * D + li * 8;
-  const uint16_t* kb = kc + head_off;
-  const uint16_t* vb = vc + head_off;
+  const typename Fmt::Elem* kb = kc + head_off;
+  const typename Fmt::Elem* vb = vc + head_off;
+  // the head's scales: its offset in keys
+  const typename Fmt::Scale ksb = Fmt::at(ksc, head_off / D), vsb = Fmt::at(vsc, head_off / D);
   for (int64_t j0 = k0; j0 < k1; j0 += decode::kKeyTile) {
-    u16x8 kr[UN], vr[UN];
+    typename Fmt::Piece kr[UN], vr[UN];
     unsigned ok[UN];  // bit t: token t of the tile attends the key
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
@@ -170,19 +303,23 @@ __global__ __launch_bounds__(decode::kThreads) void decode_attn_kernel(
       ok[u] = 0;
 #pragma unroll
       for (int t = 0; t < QT; ++t) ok[u] |= (unsigned)(j >= tk0[t] && j < tk1[t]) << t;
-      kr[u] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      kr[u] = Fmt::zero();
       vr[u] = kr[u];
       if (QT == 1 ? ok[u] != 0 : j < k1) {  // the hull: a key between two tokens' ranges is loaded
-        kr[u] = *reinterpret_cast<const u16x8*>(kb + j * D);
-        vr[u] = *reinterpret_cast<const u16x8*>(vb + j * D);
+        kr[u] = Fmt::load(kb + j * D, ksb, j);
+        vr[u] = Fmt::load(vb + j * D, vsb, j);
       }
     }
     float sc[UN][H];
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       float kf[8];
+      if constexpr (Fmt::kFp8) {
+        Fmt::widen(kr[u], kf);
+      } else {  // written out: through widen() the 16 x 128 instantiations of the bf16 format spilled
 #pragma unroll
-      for (int i = 0; i < 8; ++i) kf[i] = bf2f(kr[u][i]);
+        for (int i = 0; i < 8; ++i) kf[i] = bf2f(kr[u][i]);
+      }
 #pragma unroll
       for (int x = 0; x < H; ++x) {
         float d = 0.f;
@@ -194,9 +331,14 @@ __global__ __launch_bounds__(decode::kThreads) void decode_attn_kernel(
     }
     float vf[UN][8];
 #pragma unroll
-    for (int u = 0; u < UN; ++u)
+    for (int u = 0; u < UN; ++u) {
+      if constexpr (Fmt::kFp8) {
+        Fmt::widen(vr[u], vf[u]);
+      } else {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) vf[u][i] = bf2f(vr[u][i]);
+        for (int i = 0; i < 8; ++i) vf[u][i] = bf2f(vr[u][i]);
+      }
+    }
 #pragma unroll
     for (int x = 0; x < H; ++x) {
       float mn = m[x];
@@ -293,13 +435,49 @@ __global__ __launch_bounds__(decode::kThreads) void decode_combine_kernel(
   }
 }
 
-void check_cache(const at::Tensor& k_cache, const at::Tensor& v_cache, int64_t nkv, int64_t D, const char* name) {
-  DTG_CHECK_CUDA_BF16(k_cache);
-  DTG_CHECK_CUDA_BF16(v_cache);
+// The caches of a call and, for E4m3Cache, their scales (null for Bf16Cache).
+struct Caches {
+  const at::Tensor &k, &v;
+  const at::Tensor *k_scale = nullptr, *v_scale = nullptr;
+  template <class Fmt>
+  typename Fmt::Elem* data(const at::Tensor& t) const {
+    return reinterpret_cast<typename Fmt::Elem*>(t.data_ptr());
+  }
+  template <class Fmt>
+  typename Fmt::ScaleOut scale(const at::Tensor* t) const {
+    if constexpr (Fmt::kFp8) {
+      return t->data_ptr<float>();
+    } else {
+      return NoScale{};
+    }
+  }
+};
+
+template <class Fmt>
+void check_cache(const Caches& c, int64_t nkv, int64_t D, const char* name) {
+  const at::Tensor &k_cache = c.k, &v_cache = c.v;
+  if constexpr (Fmt::kFp8) {
+    DTG_CHECK(k_cache.is_cuda() && v_cache.is_cuda() && k_cache.scalar_type() == at::kFloat8_e4m3fn &&
+                  v_cache.scalar_type() == at::kFloat8_e4m3fn,
+              name, ": caches must be float8_e4m3fn GPU tensors");
+  } else {
+    DTG_CHECK_CUDA_BF16(k_cache);
+    DTG_CHECK_CUDA_BF16(v_cache);
+  }
   DTG_CHECK(k_cache.dim() == 4 && k_cache.is_contiguous() && v_cache.is_contiguous() &&
                 k_cache.sizes() == v_cache.sizes() && k_cache.size(1) == nkv && k_cache.size(3) == D,
-            name, ": caches must be contiguous bf16 [rows_max, nkv, S_max, head_dim]");
+            name, ": caches must be contiguous ", Fmt::kFp8 ? "float8_e4m3fn" : "bf16",
+            " [rows_max, nkv, S_max, head_dim]");
   DTG_CHECK(k_cache.numel() < (int64_t(1) << 46), name, ": cache too large");
+  if constexpr (Fmt::kFp8) {
+    for (const at::Tensor* s : {c.k_scale, c.v_scale})
+      DTG_CHECK(s->is_cuda() && s->scalar_type() == at::kFloat && s->is_contiguous() && s->dim() == 3 &&
+                    s->sizes() == k_cache.sizes().slice(0, 3),
+                name, ": scales must be contiguous f32 GPU tensors [rows_max, nkv, S_max]");
+    DTG_CHECK(reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 8 == 0,
+              name, ": caches must be 8-B aligned");
+  }
 }
 
 void check_qkv(const at::Tensor& qkv, int64_t nq, int64_t nkv, int64_t D, const char* name) {
@@ -312,15 +490,13 @@ void check_index(const at::Tensor& t, int64_t n, const char* name, const char* w
             " must be an int32 GPU tensor with one entry per ", per);
 }
 
-}  // namespace
-
-void kv_cache_append_(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                      const at::Tensor& cos_t, const at::Tensor& sin_t, const at::Tensor& pos, const at::Tensor& rows,
-                      int64_t nq, int64_t nkv, int64_t head_dim) {
-  const char* name = "kv_cache_append_";
-  const int64_t D = head_dim;
+template <class Fmt>
+void append_launch(const char* name, const at::Tensor& qkv, const Caches& c, const at::Tensor& cos_t,
+                   const at::Tensor& sin_t, const at::Tensor& pos, const at::Tensor& rows, int64_t nq, int64_t nkv,
+                   int64_t D) {
+  const at::Tensor &k_cache = c.k, &v_cache = c.v;
   check_qkv(qkv, nq, nkv, D, name);
-  check_cache(k_cache, v_cache, nkv, D, name);
+  check_cache<Fmt>(c, nkv, D, name);
   const int64_t T = qkv.size(0);
   check_index(rows, T, name, "rows");
   rope::check_pos(pos, T, name);
@@ -332,24 +508,25 @@ void kv_cache_append_(const at::Tensor& qkv, const at::Tensor& k_cache, const at
   DTG_CHECK(nblk < (int64_t(1) << 31), name, ": too many tokens");
   const float* cp = rope ? cos_t.data_ptr<float>() : nullptr;
   const float* sp = rope ? sin_t.data_ptr<float>() : nullptr;
-  DTG_HD_RP_DISPATCH(D, rope, kv_append_kernel<HD, RP><<<(unsigned)nblk, 256, 0, stream()>>>(
-                                  bf16_mut(qkv), qkv.stride(0), bf16_mut(k_cache), bf16_mut(v_cache), cp, sp, max_pos,
+  DTG_HD_RP_DISPATCH(D, rope, kv_append_kernel<Fmt, HD, RP><<<(unsigned)nblk, 256, 0, stream()>>>(
+                                  bf16_mut(qkv), qkv.stride(0), c.data<Fmt>(k_cache), c.data<Fmt>(v_cache),
+                                  c.scale<Fmt>(c.k_scale), c.scale<Fmt>(c.v_scale), cp, sp, max_pos,
                                   pos.data_ptr<int64_t>(), rows.data_ptr<int32_t>(), (int)nq, (int)nkv, T,
                                   k_cache.size(0), k_cache.size(2)));
   DTG_LAUNCH_CHECK();
 }
 
-namespace {
-
 // decode_attn (Q = 1) and decode_attn_multi: qkv holds Q tokens for each of rows.numel() sequences, lens
 // one entry per token.  Q = 1 runs the one-token kernel, Q > 1 the tile of decode::q_tile(G) tokens.
-at::Tensor decode_launch(const char* name, const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                         const at::Tensor& rows, const at::Tensor& lens, int64_t Q, int64_t nq, int64_t nkv, int64_t D,
-                         double scale, int64_t max_len, int64_t window, int64_t splits) {
+template <class Fmt>
+at::Tensor decode_launch(const char* name, const at::Tensor& qkv, const Caches& c, const at::Tensor& rows,
+                         const at::Tensor& lens, int64_t Q, int64_t nq, int64_t nkv, int64_t D, double scale,
+                         int64_t max_len, int64_t window, int64_t splits) {
+  const at::Tensor &k_cache = c.k, &v_cache = c.v;
   check_qkv(qkv, nq, nkv, D, name);
   const int64_t G = nq / nkv;
   DTG_CHECK(decode::group_ok(G), name, ": query heads per kv head must be one of 1, 2, 3, 4, 7, 8, 16");
-  check_cache(k_cache, v_cache, nkv, D, name);
+  check_cache<Fmt>(c, nkv, D, name);
   const int64_t T = qkv.size(0), S_max = k_cache.size(2);
   DTG_CHECK(Q >= 1 && Q < (int64_t(1) << 20) && T % Q == 0, name, ": q_len must be >= 1 and divide the rows of qkv");
   const int64_t B = T / Q;
@@ -372,10 +549,10 @@ at::Tensor decode_launch(const char* name, const at::Tensor& qkv, const at::Tens
     ws_ml = ws_o + T * nkv * p.splits * G * D;
   }
 #define DTG_DECODE_LAUNCH(D_, G_, QT_)                                                                              \
-  decode_attn_kernel<D_, G_, QT_><<<(unsigned)nwg, decode::kThreads, 0, stream()>>>(                                \
-      bf16_ptr(qkv), qkv.stride(0), bf16_ptr(k_cache), bf16_ptr(v_cache), rows.data_ptr<int32_t>(),                 \
-      lens.data_ptr<int32_t>(), ws_o, ws_ml, bf16_mut(out), (int)nkv, p.splits, p.chunk, window, k_cache.size(0), \
-      S_max, (float)scale, (int)Q)
+  decode_attn_kernel<Fmt, D_, G_, QT_><<<(unsigned)nwg, decode::kThreads, 0, stream()>>>(                           \
+      bf16_ptr(qkv), qkv.stride(0), c.data<Fmt>(k_cache), c.data<Fmt>(v_cache), rows.data_ptr<int32_t>(),           \
+      lens.data_ptr<int32_t>(), ws_o, ws_ml, bf16_mut(out), (int)nkv, p.splits, p.chunk, window, k_cache.size(0),   \
+      S_max, (float)scale, (int)Q, c.scale<Fmt>(c.k_scale), c.scale<Fmt>(c.v_scale))
 #define DTG_DECODE_GQ(D_, G_, QT_)                \
   if (Q == 1) {                                   \
     DTG_DECODE_LAUNCH(D_, G_, 1);                 \
@@ -409,24 +586,49 @@ at::Tensor decode_launch(const char* name, const at::Tensor& qkv, const at::Tens
 
 }  // namespace
 
+void kv_cache_append_(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                      const at::Tensor& cos_t, const at::Tensor& sin_t, const at::Tensor& pos, const at::Tensor& rows,
+                      int64_t nq, int64_t nkv, int64_t head_dim) {
+  append_launch<Bf16Cache>("kv_cache_append_", qkv, {k_cache, v_cache}, cos_t, sin_t, pos, rows, nq, nkv, head_dim);
+}
+
+void kv_cache_append_fp8_(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                          const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& cos_t,
+                          const at::Tensor& sin_t, const at::Tensor& pos, const at::Tensor& rows, int64_t nq,
+                          int64_t nkv, int64_t head_dim) {
+  append_launch<E4m3Cache>("kv_cache_append_fp8_", qkv, {k_cache, v_cache, &k_scale, &v_scale}, cos_t, sin_t, pos,
+                           rows, nq, nkv, head_dim);
+}
+
 at::Tensor decode_attn(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
                        const at::Tensor& rows, const at::Tensor& lens, int64_t nq, int64_t nkv, int64_t head_dim,
                        double scale, int64_t max_len, int64_t window, int64_t splits) {
-  return decode_launch("decode_attn", qkv, k_cache, v_cache, rows, lens, 1, nq, nkv, head_dim, scale, max_len, window,
-                       splits);
+  return decode_launch<Bf16Cache>("decode_attn", qkv, {k_cache, v_cache}, rows, lens, 1, nq, nkv, head_dim, scale,
+                                  max_len, window, splits);
 }
 
 at::Tensor decode_attn_multi(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
                              const at::Tensor& rows, const at::Tensor& lens, int64_t q_len, int64_t nq, int64_t nkv,
                              int64_t head_dim, double scale, int64_t max_len, int64_t window, int64_t splits) {
-  return decode_launch("decode_attn_multi", qkv, k_cache, v_cache, rows, lens, q_len, nq, nkv, head_dim, scale, max_len,
-                       window, splits);
+  return decode_launch<Bf16Cache>("decode_attn_multi", qkv, {k_cache, v_cache}, rows, lens, q_len, nq, nkv, head_dim,
+                                  scale, max_len, window, splits);
+}
+
+// q_len = 1: the one-token kernel; q_len > 1: the tile of decode::q_tile(G) tokens
+at::Tensor decode_attn_fp8(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                           const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& rows,
+                           const at::Tensor& lens, int64_t q_len, int64_t nq, int64_t nkv, int64_t head_dim,
+                           double scale, int64_t max_len, int64_t window, int64_t splits) {
+  return decode_launch<E4m3Cache>("decode_attn_fp8", qkv, {k_cache, v_cache, &k_scale, &v_scale}, rows, lens, q_len,
+                                  nq, nkv, head_dim, scale, max_len, window, splits);
 }
 
 TORCH_LIBRARY_IMPL(dtg, CUDA, m) {
   m.impl("kv_cache_append_", &kv_cache_append_);
+  m.impl("kv_cache_append_fp8_", &kv_cache_append_fp8_);
   m.impl("decode_attn", &decode_attn);
   m.impl("decode_attn_multi", &decode_attn_multi);
+  m.impl("decode_attn_fp8", &decode_attn_fp8);
 }
 
 }  // namespace dtg

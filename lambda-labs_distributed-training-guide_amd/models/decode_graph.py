@@ -41,7 +41,8 @@ _NO_EOS = -(2 ** 62)  # no id equals it
 class GraphedDecode:
     """The captured decode loop of `model` for `n` sequences and a cache of `s_max` positions."""
 
-    def __init__(self, model, n: int, s_max: int, linear: str = "skinny", warmup: int = 2, fp8=None):
+    def __init__(self, model, n: int, s_max: int, linear: str = "skinny", warmup: int = 2, fp8=None,
+                 kv_cache: str = "bf16"):
         _g._check_model(model)
         _g._check_linear(linear, n)
         dev = model.embed_tokens.weight.device
@@ -49,7 +50,8 @@ class GraphedDecode:
             raise ValueError("GraphedDecode needs a GPU (HIP-graph capture)")
         self.model, self.n, self.s_max, self.linear, self.warmup = model, int(n), int(s_max), linear, int(warmup)
         self.fp8 = _g._check_fp8(model, linear, fp8, build=True)  # linear="skinny-fp8": static device tensors
-        self.cache = _g.KVCache(model.config, self.n, self.s_max, device=dev, dtype=model.embed_tokens.weight.dtype)
+        self.cache = _g.KVCache(model.config, self.n, self.s_max, device=dev, dtype=model.embed_tokens.weight.dtype,
+                                kv_cache=kv_cache)  # "fp8": codes and scales are static device tensors too
         i64 = dict(dtype=torch.long, device=dev)
         self.rows = torch.arange(self.n, dtype=torch.int32, device=dev)
         self.tok = torch.zeros(self.n, **i64)             # the ids the next step embeds

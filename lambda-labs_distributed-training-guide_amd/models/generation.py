@@ -42,17 +42,43 @@ def _check_model(model):
 class KVCache:
     """Per-layer K / V tensors [rows_max, nkv, S_max, D] (head-major: one kv head's keys are contiguous
     along the sequence), the device-side length of every row, and a host upper bound of those lengths
-    for the decode kernel's launch plan."""
+    for the decode kernel's launch plan.
 
-    def __init__(self, cfg, rows_max: int, s_max: int, device=None, dtype=torch.bfloat16):
+    kv_cache="fp8": K / V are float8_e4m3fn with one f32 power-of-two scale per (row, kv head, position) in the
+    lists `k_scale` / `v_scale` ([rows_max, nkv, S_max] per layer; None for "bf16"): (D + 4) / (2 D) of the bf16
+    cache's bytes.  `ops.kv_cache_append` quantises what it writes and the decode attention reads the codes; the
+    cache is exactly some bf16 cache, and prompt and decode steps attend the same quantised values."""
+
+    def __init__(self, cfg, rows_max: int, s_max: int, device=None, dtype=torch.bfloat16, kv_cache: str = "bf16"):
         if rows_max < 1 or s_max < 1:
             raise ValueError(f"KVCache: rows_max ({rows_max}) and S_max ({s_max}) must be positive")
-        self.rows_max, self.s_max = int(rows_max), int(s_max)
+        _check_kv_cache(kv_cache)
+        self.rows_max, self.s_max, self.kv_cache = int(rows_max), int(s_max), kv_cache
         shape = (self.rows_max, cfg.num_key_value_heads, self.s_max, cfg.head_dim)
-        self.k = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(cfg.num_hidden_layers)]
-        self.v = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(cfg.num_hidden_layers)]
+        layers = range(cfg.num_hidden_layers)
+        if kv_cache == "fp8":
+            def codes():
+                return torch.zeros(shape, device=device, dtype=torch.uint8).view(torch.float8_e4m3fn)
+
+            self.k, self.v = [codes() for _ in layers], [codes() for _ in layers]
+            self.k_scale = [torch.ones(shape[:3], device=device, dtype=torch.float32) for _ in layers]
+            self.v_scale = [torch.ones(shape[:3], device=device, dtype=torch.float32) for _ in layers]
+        else:
+            self.k = [torch.zeros(shape, device=device, dtype=dtype) for _ in layers]
+            self.v = [torch.zeros(shape, device=device, dtype=dtype) for _ in layers]
+            self.k_scale = self.v_scale = None
         self.lens = torch.zeros(self.rows_max, dtype=torch.int32, device=device)
         self.max_len = 0  # host: no row is longer than this
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the K / V tensors and, for an FP8 cache, their scales."""
+        ts = self.k + self.v + (self.k_scale or []) + (self.v_scale or [])
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    def scales(self, i):
+        """The keyword arguments of layer i's scales for the cache ops (empty for a bf16 cache)."""
+        return {} if self.k_scale is None else dict(k_scale=self.k_scale[i], v_scale=self.v_scale[i])
 
     def reset(self):
         self.lens.zero_()
@@ -60,6 +86,12 @@ class KVCache:
 
 
 LINEAR_MODES = ("blas", "skinny", "skinny-fp8")
+KV_CACHE_MODES = ("bf16", "fp8")
+
+
+def _check_kv_cache(kv_cache):
+    if kv_cache not in KV_CACHE_MODES:
+        raise ValueError(f"kv_cache must be one of {KV_CACHE_MODES}, got {kv_cache!r}")
 
 
 def _check_linear(linear, n=None):
@@ -148,9 +180,10 @@ def _append(attn, qkv, cache, i, cos, sin, pos, rows, pos_max, rope_pos=None):
     if attn.qk_norm:
         qkv = ops.qk_norm_rope(qkv, attn.q_norm.weight, attn.k_norm.weight, attn.eps, attn.nq, attn.nkv, attn.d,
                                cos, sin, pos if rope_pos is None else rope_pos)
-        return ops.kv_cache_append(qkv, cache.k[i], cache.v[i], pos, rows, attn.nq, attn.nkv, attn.d, pos_max=pos_max)
+        return ops.kv_cache_append(qkv, cache.k[i], cache.v[i], pos, rows, attn.nq, attn.nkv, attn.d, pos_max=pos_max,
+                                   **cache.scales(i))
     return ops.kv_cache_append(qkv, cache.k[i], cache.v[i], pos, rows, attn.nq, attn.nkv, attn.d, cos, sin,
-                               pos_max=pos_max)
+                               pos_max=pos_max, **cache.scales(i))
 
 
 def _last_logits(model, x, res, linear="blas", fp8=None):
@@ -218,7 +251,7 @@ def _decode_body(model, tokens, cache, rows_t, plan_len, linear, fp8=None):
     def attend(i, attn, qkv):
         qkv = _append(attn, qkv, cache, i, cos, sin, pos, rows_t, plan_len - 1)
         return ops.decode_attention(qkv, cache.k[i], cache.v[i], rows_t, new_lens, attn.nq, attn.nkv, attn.d, plan_len,
-                                    window=attn.window)
+                                    window=attn.window, **cache.scales(i))
 
     x, res = _run_layers(model, ops.embedding(tokens, model.embed_tokens.weight), attend, linear, fp8)
     cache.lens[rows_t.long()] = new_lens
@@ -302,7 +335,7 @@ def extend_step(model, tokens: torch.Tensor, q_valid: torch.Tensor, cache: KVCac
     def attend(i, attn, qkv):
         qkv = _append(attn, qkv, cache, i, cos, sin, pos, tok_rows, plan_len - 1, rope_pos)
         return ops.decode_attention_multi(qkv, cache.k[i], cache.v[i], rows_t, lens, Q, attn.nq, attn.nkv, attn.d,
-                                          plan_len, window=attn.window)
+                                          plan_len, window=attn.window, **cache.scales(i))
 
     x, res = _run_layers(model, ops.embedding(tokens.reshape(-1).to(dev), model.embed_tokens.weight), attend, linear, fp8)
     return _last_logits(model, x, res, linear, fp8)
@@ -354,7 +387,7 @@ def _fused_params(n, **given):
 def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              top_p: float = 1.0, eos_token_id: Optional[int] = None, seed: int = 0, s_max: Optional[int] = None,
              min_p: float = 0.0, sampler: str = "torch", linear: str = "blas", decode="eager",
-             bucketed: bool = False, fp8=None, speculate=None) -> List[torch.Tensor]:
+             bucketed: bool = False, fp8=None, speculate=None, kv_cache: str = "bf16") -> List[torch.Tensor]:
     """Continue every prompt by up to `max_new_tokens` ids; returns the new ids of each sequence (1-D
     int64 tensors on the CPU), ending with `eos_token_id` where the sequence produced it.
 
@@ -384,8 +417,13 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     decoding with exact-match verification.  Every step runs the last accepted id and up to k - 1 drafted ids
     of each row through one `extend_step` and keeps the drafted ids that equal the model's own id of their
     position.  Eager only; sampling needs sampler="fused".  With linear="skinny" / "skinny-fp8" (at most
-    SKINNY_MAX_M rows: prompts x k) the ids are those of the plain loop planned for the same length, bit for bit."""
+    SKINNY_MAX_M rows: prompts x k) the ids are those of the plain loop planned for the same length, bit for bit.
+
+    kv_cache="fp8": the KV cache is e4m3 with one power-of-two scale per key vector (`KVCache`), about half the
+    bytes; it composes with every `linear`, `decode` and `speculate` choice, and the bitwise promises above hold
+    among the runs that use it."""
     _check_model(model)
+    _check_kv_cache(kv_cache)
     prompts = [p.reshape(-1) for p in prompts]
     if not prompts or min(p.numel() for p in prompts) < 1:
         raise ValueError("generate: every prompt needs at least one token")
@@ -436,15 +474,19 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     if graphed:
         from .decode_graph import GraphedDecode
 
-        gd = decode if isinstance(decode, GraphedDecode) else GraphedDecode(model, n, s_max, linear=linear, fp8=fp8)
+        gd = decode if isinstance(decode, GraphedDecode) else GraphedDecode(model, n, s_max, linear=linear, fp8=fp8,
+                                                                            kv_cache=kv_cache)
         if fp8 is not None and gd.fp8 is not fp8:
             raise ValueError("generate: the GraphedDecode was captured with other fp8 weights")
+        if gd.cache.kv_cache != kv_cache:
+            raise ValueError(f"generate: the GraphedDecode holds a {gd.cache.kv_cache} cache, kv_cache={kv_cache!r} was asked for")
         return gd.run(prompts, max_new_tokens, fused, seed, eos_token_id, s_max=s_max, linear=linear)
     fp8 = _check_fp8(model, linear, fp8, build=True)
     if speculate is not None:
         from .speculative import speculative_loop
 
-        return speculative_loop(model, prompts, max_new_tokens, speculate, fused, seed, eos_token_id, s_max, linear, fp8)
+        return speculative_loop(model, prompts, max_new_tokens, speculate, fused, seed, eos_token_id, s_max, linear, fp8,
+                                kv_cache)
     gen = None
     if fused is not None:
         fused = {k: torch.tensor(v, dtype=torch.int32 if k == "top_k" else torch.float32, device=dev)
@@ -454,7 +496,7 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     elif temperature > 0.0:
         gen = torch.Generator(device=dev)
         gen.manual_seed(int(seed))
-    cache = KVCache(model.config, n, s_max, device=dev, dtype=model.embed_tokens.weight.dtype)
+    cache = KVCache(model.config, n, s_max, device=dev, dtype=model.embed_tokens.weight.dtype, kv_cache=kv_cache)
     out = torch.zeros(n, max_new_tokens, dtype=torch.long, device=dev)
     count = torch.zeros(n, dtype=torch.long, device=dev)  # ids kept per sequence
     done = torch.zeros(n, dtype=torch.bool, device=dev)

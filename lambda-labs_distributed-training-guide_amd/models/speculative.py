@@ -98,7 +98,8 @@ def _accept(drafts: Sequence[int], target: Sequence[int]) -> int:
     return a
 
 
-def speculative_loop(model, prompts, max_new_tokens, spec, fused, seed, eos_token_id, s_max, linear, fp8):
+def speculative_loop(model, prompts, max_new_tokens, spec, fused, seed, eos_token_id, s_max, linear, fp8,
+                     kv_cache="bf16"):
     """generate()'s loop under `spec`; arguments as generate() has checked them (`fused`: the per-prompt host lists
     of the fused sampler's parameters, or None for argmax)."""
     from .generation import KVCache, decode_bucket, extend_step, prefill
@@ -107,7 +108,7 @@ def speculative_loop(model, prompts, max_new_tokens, spec, fused, seed, eos_toke
     dev = model.embed_tokens.weight.device
     stats = spec.stats = dict(steps=0, proposed=0, accepted=0, tokens=0)
     plan_len = decode_bucket(max(p.numel() for p in prompts) + max_new_tokens, s_max)
-    cache = KVCache(model.config, n, s_max, device=dev, dtype=model.embed_tokens.weight.dtype)
+    cache = KVCache(model.config, n, s_max, device=dev, dtype=model.embed_tokens.weight.dtype, kv_cache=kv_cache)
     if fused is not None:
         col = lambda name, reps: torch.tensor(fused[name], dtype=torch.int32 if name == "top_k" else torch.float32,  # noqa: E731
                                               device=dev).repeat_interleave(reps)

@@ -118,16 +118,88 @@ def kv_cache_append_(qkv, k_cache, v_cache, cos, sin, pos, rows, nq, nkv, head_d
     v_cache[rows[ok], :, pos[ok]] = v[ok]
 
 
+def _check_fp8_cache(name, k_cache, v_cache, k_scale, v_scale):
+    if k_cache.dtype != torch.float8_e4m3fn or v_cache.dtype != torch.float8_e4m3fn:
+        raise RuntimeError(f"dtg: {name}: caches must be float8_e4m3fn tensors")
+    for s in (k_scale, v_scale):
+        if s.dtype != torch.float32 or s.shape != k_cache.shape[:3] or not s.is_contiguous():
+            raise RuntimeError(f"dtg: {name}: scales must be contiguous f32 tensors [rows_max, nkv, S_max]")
+
+
+def _e4m3_vectors(x):
+    """x f32 [..., D] -> (e4m3 codes as uint8 [..., D], scale f32 [...]): one power-of-two scale per vector, the
+    one that puts amax into (224, 448], read off amax's exponent bits as the append kernel does (a significand
+    up to 1.75 = 448 / 256 goes to [256, 448] with 2^(E - 135), a larger one to (224, 256) with 2^(E - 134));
+    floored at 2^-100, 1 for an all-zero vector.  The quotient is clamped to +-448 by comparisons, which a NaN
+    passes, and rounded to nearest even by the cast."""
+    amax = torch.nan_to_num(x.abs(), nan=0.0).amax(-1)
+    bits = amax.view(torch.int32)
+    k = (bits >> 23) - 134 - ((bits & 0x7FFFFF) <= 0x600000).to(torch.int32)
+    k = torch.where(amax == 0, torch.zeros_like(k), k.clamp_min(-100)).to(torch.int32)
+    scale = ((k + 127) << 23).view(torch.float32)
+    q = x * ((127 - k) << 23).view(torch.float32)[..., None]
+    q = torch.where(q > 448.0, 448.0, torch.where(q < -448.0, -448.0, q))
+    return q.to(torch.float8_e4m3fn).view(torch.uint8), scale
+
+
+def kv_cache_append_fp8_(qkv, k_cache, v_cache, k_scale, v_scale, cos, sin, pos, rows, nq, nkv, head_dim):
+    """kv_cache_append_ into an e4m3 cache: the roped k and the v of every in-range token are quantised per
+    (token, kv head) vector, codes and scales go to cache / scale[rows[t], :, pos[t]], and the dequantised
+    values (code * scale, exact in bf16) replace k and v in qkv (csrc/kernels/decode_attn.hip)."""
+    T, d = qkv.shape[0], head_dim
+    _check_fp8_cache("kv_cache_append_fp8_", k_cache, v_cache, k_scale, v_scale)
+    if not (k_cache.dim() == 4 and k_cache.shape == v_cache.shape and k_cache.shape[1] == nkv and k_cache.shape[3] == d):
+        raise RuntimeError("dtg: kv_cache_append_fp8_: caches must be contiguous float8_e4m3fn [rows_max, nkv, S_max, head_dim]")
+    if not (qkv.dim() == 2 and qkv.shape[1] >= (nq + 2 * nkv) * d and pos.numel() == T and rows.numel() == T):
+        raise RuntimeError("dtg: kv_cache_append_fp8_: qkv must be [T, (nq + 2 nkv) * head_dim] with one pos and row per token")
+    pos, rows = pos.long(), rows.long()
+    ok = (pos >= 0) & (pos < k_cache.shape[2]) & (rows >= 0) & (rows < k_cache.shape[0])
+    if cos.numel():
+        ok &= pos < cos.shape[0]
+        sel = qkv[ok]
+        rope_(sel, cos, sin, pos[ok], nq + nkv, d, False)
+        qkv[ok] = sel
+    n = int(ok.sum())
+    for cache, scales, c0 in ((k_cache, k_scale, nq * d), (v_cache, v_scale, (nq + nkv) * d)):
+        codes, s = _e4m3_vectors(qkv[ok, c0:c0 + nkv * d].float().reshape(n, nkv, d))
+        cache.view(torch.uint8)[rows[ok], :, pos[ok]] = codes
+        scales[rows[ok], :, pos[ok]] = s
+        deq = codes.view(torch.float8_e4m3fn).float() * s[..., None]
+        qkv[ok, c0:c0 + nkv * d] = deq.reshape(n, nkv * d).to(qkv.dtype)
+
+
+def decode_attn_fp8(qkv, k_cache, v_cache, k_scale, v_scale, rows, lens, q_len, nq, nkv, head_dim, scale, max_len,
+                    window, splits):
+    """decode_attn (q_len = 1) / decode_attn_multi (q_len > 1) on an e4m3 cache: a key vector is
+    float(code) * its scale, exactly a bf16 value; only the attended keys and their scales are read."""
+    _check_fp8_cache("decode_attn_fp8", k_cache, v_cache, k_scale, v_scale)
+    if q_len < 1 or qkv.shape[0] % q_len or rows.numel() * q_len != qkv.shape[0] or lens.numel() != qkv.shape[0]:
+        raise RuntimeError("dtg: decode_attn_fp8: qkv and lens need q_len >= 1 rows per entry of rows")
+
+    def load(r, lo, n):
+        return (k_cache[r, :, lo:n].float() * k_scale[r, :, lo:n, None], v_cache[r, :, lo:n].float() * v_scale[r, :, lo:n, None])
+
+    return _decode_rows("decode_attn_fp8", qkv, k_cache, v_cache, load, rows.repeat_interleave(q_len), lens, nq, nkv,
+                        head_dim, scale, max_len, window)
+
+
 def decode_attn(qkv, k_cache, v_cache, rows, lens, nq, nkv, head_dim, scale, max_len, window=0, splits=0):
     """One query token per sequence against keys [max(0, len - window), len) of its cache row, f32
     softmax, one rounding.  The CPU reference takes any head dim and group size; `splits` has no
     meaning here (one pass)."""
+    return _decode_rows("decode_attn", qkv, k_cache, v_cache,
+                        lambda r, lo, n: (k_cache[r, :, lo:n].float(), v_cache[r, :, lo:n].float()), rows, lens, nq, nkv,
+                        head_dim, scale, max_len, window)
+
+
+def _decode_rows(name, qkv, k_cache, v_cache, load, rows, lens, nq, nkv, head_dim, scale, max_len, window):
+    """decode_attn's loop; load(r, lo, n) returns the f32 keys and values [nkv, n - lo, D] of cache row r."""
     B, d, g = qkv.shape[0], head_dim, nq // nkv
     if nq % nkv or not (k_cache.dim() == 4 and k_cache.shape == v_cache.shape and k_cache.shape[1] == nkv
                         and k_cache.shape[3] == d):
-        raise RuntimeError("dtg: decode_attn: caches must be contiguous bf16 [rows_max, nkv, S_max, head_dim]")
+        raise RuntimeError(f"dtg: {name}: caches must be contiguous [rows_max, nkv, S_max, head_dim]")
     if not 0 <= max_len <= k_cache.shape[2]:
-        raise RuntimeError("dtg: decode_attn: max_len must lie in [0, S_max]")
+        raise RuntimeError(f"dtg: {name}: max_len must lie in [0, S_max]")
     out = torch.zeros(B, nq * d, dtype=qkv.dtype)
     for b in range(B):
         n, r = int(lens[b]), int(rows[b])
@@ -138,7 +210,7 @@ def decode_attn(qkv, k_cache, v_cache, rows, lens, nq, nkv, head_dim, scale, max
         if n <= lo:
             continue
         q = qkv[b, : nq * d].float().reshape(nkv, g, d)
-        k, v = k_cache[r, :, lo:n].float(), v_cache[r, :, lo:n].float()
+        k, v = load(r, lo, n)
         p = torch.softmax(torch.einsum("hgd,hsd->hgs", q, k) * scale, -1)
         out[b] = torch.einsum("hgs,hsd->hgd", p, v).reshape(nq * d).to(qkv.dtype)
     return out
@@ -845,5 +917,6 @@ for _name, _fn in list(globals().items()):
         "flash_attn_bwd_qkv_rope", "flash_attn_tuning", "layernorm_fwd", "dropout_add_layernorm_fwd", "layernorm_bwd",
         "gelu_fwd", "gelu_bwd", "gelu_bwd_t", "qk_norm_rope_fwd_", "qk_norm_rope_bwd_", "kv_cache_append_", "decode_attn",
         "sample_logits", "skinny_linear", "skinny_linear_fp8", "decode_attn_multi",
+        "kv_cache_append_fp8_", "decode_attn_fp8",
     ):
         LIB.impl(_name, _fn, "CPU")

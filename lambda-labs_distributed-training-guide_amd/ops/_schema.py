@@ -51,6 +51,16 @@ _DEFS = [
     # alone with the same max_len and splits.  The keys between the ranges of one sequence's tokens are read too.
     "decode_attn_multi(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor rows, Tensor lens, int q_len, int nq, "
     "int nkv, int head_dim, float scale, int max_len, int window, int splits) -> Tensor",
+    # the same two on an FP8 cache (the kernels' e4m3 cache format): k_cache / v_cache float8_e4m3fn (OCP)
+    # [rows_max, nkv, S_max, D], k_scale / v_scale f32 [rows_max, nkv, S_max], one scale per key vector: the power
+    # of two that puts the vector's amax into (224, 448] (ops.quantize_fp8_rows(pow2=True) of the D-vector, bit for
+    # bit; for k, of the roped k).  The append also writes the dequantised k / v (code * scale, exact in bf16) back
+    # into qkv.  decode_attn_fp8 is decode_attn at q_len = 1 and decode_attn_multi at q_len > 1, and returns bit
+    # for bit what they return on the dequantised bf16 caches
+    "kv_cache_append_fp8_(Tensor(a!) qkv, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor(d!) k_scale, "
+    "Tensor(e!) v_scale, Tensor cos, Tensor sin, Tensor pos, Tensor rows, int nq, int nkv, int head_dim) -> ()",
+    "decode_attn_fp8(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor rows, "
+    "Tensor lens, int q_len, int nq, int nkv, int head_dim, float scale, int max_len, int window, int splits) -> Tensor",
     # fused top-k / top-p / min-p sampling (csrc/kernels/sample.hip): logits [n, V] bf16 / f32 with unit
     # inner stride; params f32 [n, 3] = temperature, top_p, min_p; top_k int32 [n]; rng int64 [n, 3] =
     # seed, stream, step of the row's Philox draw; u f32 [n] in [0, 1) replaces that draw.  Returns

@@ -498,6 +498,12 @@ def attention(qkv, nq, nkv, head_dim, cu_seqlens, max_seqlen, cos=None, sin=None
 # Inference only (no autograd).  DTG_DECODE_FUSED=0 composes both ops from torch ops instead (the
 # kernels' A/B partner and the yardstick of their accuracy tests); so do, on a GPU, dtypes other than
 # bf16 and head dims and group sizes the kernels are not instantiated for.
+#
+# FP8 cache: the three ops take `k_scale` / `v_scale` (None = the bf16 cache, today's path byte for byte).
+# With scales the caches are float8_e4m3fn [rows_max, nkv, S_max, D] and the scales f32 [rows_max, nkv, S_max],
+# one per key vector, by the rule of `quantize_fp8_rows(pow2=True)` on the D-vector; the append also writes
+# the dequantised k / v back into qkv.  The compositions dequantise (`cache.float() * scale[..., None]` into
+# qkv's dtype) and run as for bf16; the composed append quantises with `quantize_fp8_rows`.
 _DECODE_FUSED = os.environ.get("DTG_DECODE_FUSED", "1") == "1"
 DECODE_GROUPS = (1, 2, 3, 4, 7, 8, 16)  # query heads per kv head the decode kernel is instantiated for
 
@@ -508,7 +514,7 @@ def _decode_kernels(qkv, nq, nkv, d):
     return not qkv.is_cuda or (qkv.dtype == torch.bfloat16 and d in FA_HEAD_DIMS and nq // nkv in DECODE_GROUPS)
 
 
-def _check_cache_args(name, qkv, k_cache, v_cache, nq, nkv, d, index):
+def _check_cache_args(name, qkv, k_cache, v_cache, nq, nkv, d, index, k_scale=None, v_scale=None):
     if nq < 1 or nkv < 1 or nq % nkv:
         raise ValueError(f"{name}: nq ({nq}) must be a positive multiple of nkv ({nkv})")
     if qkv.dim() != 2 or qkv.shape[1] != (nq + 2 * nkv) * d:
@@ -516,25 +522,49 @@ def _check_cache_args(name, qkv, k_cache, v_cache, nq, nkv, d, index):
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[1] != nkv or k_cache.shape[3] != d:
         raise ValueError(f"{name}: caches must be [rows_max, {nkv}, S_max, {d}], got {tuple(k_cache.shape)} / "
                          f"{tuple(v_cache.shape)}")
-    if k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype or not (k_cache.is_contiguous() and v_cache.is_contiguous()):
-        raise ValueError(f"{name}: caches must be contiguous and of qkv's dtype")
+    if (k_scale is None) != (v_scale is None):
+        raise ValueError(f"{name}: pass both k_scale and v_scale (an FP8 cache), or neither")
+    fp8 = torch.float8_e4m3fn
+    if k_scale is None:
+        if k_cache.dtype == fp8 or v_cache.dtype == fp8:
+            raise ValueError(f"{name}: float8_e4m3fn caches need k_scale and v_scale")
+        if k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype or not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+            raise ValueError(f"{name}: caches must be contiguous and of qkv's dtype")
+    else:
+        if k_cache.dtype != fp8 or v_cache.dtype != fp8 or not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+            raise ValueError(f"{name}: k_scale / v_scale were given, so k_cache and v_cache must be contiguous "
+                             f"float8_e4m3fn tensors, got {k_cache.dtype} / {v_cache.dtype}")
+        for what, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if t.dtype != torch.float32 or t.shape != k_cache.shape[:3] or not t.is_contiguous():
+                raise ValueError(f"{name}: {what} must be a contiguous f32 tensor {tuple(k_cache.shape[:3])}, got "
+                                 f"{t.dtype} {tuple(t.shape)}")
     for what, t in index.items():
         if t.dim() != 1 or t.numel() != qkv.shape[0] or t.dtype not in (torch.int32, torch.int64):
             raise ValueError(f"{name}: {what} must be an integer tensor [{qkv.shape[0]}], got {t.dtype} {tuple(t.shape)}")
 
 
+def _dequantized(cache, scale, dtype):
+    """The cache an FP8 cache stands for, in `dtype` (exact in bf16); slots never written may hold anything."""
+    return (cache.float() * scale[..., None]).to(dtype)
+
+
 @torch.no_grad()
 def kv_cache_append(qkv, k_cache, v_cache, pos, rows, nq, nkv, head_dim, cos=None, sin=None, pos_max=None,
-                    row_max=None):
+                    row_max=None, k_scale=None, v_scale=None):
     """Rotate the q and k heads of the fused `qkv` [T, (nq + 2 nkv) * d] in place at `pos` (cos / sin
     given; None = already roped, as after `qk_norm_rope`) and write every token's k and v to
     cache[rows[t], :, pos[t], :].  Serves the packed prefill and a decode step alike.  Returns qkv.
     `pos` / `rows` are device tensors and are not read on the host.  A caller that knows them on the
     host passes `pos_max` / `row_max`, the largest position / row of the call: they are checked here
     against S_max, the tables and rows_max (models/generation.py does).  Without them a token outside
-    the cache silently writes nothing."""
+    the cache silently writes nothing.
+
+    `k_scale` / `v_scale` (f32 [rows_max, nkv, S_max]; the caches are then float8_e4m3fn): every k (after
+    RoPE) and v vector is quantised with its own power-of-two scale, `quantize_fp8_rows(pow2=True)` of the
+    D-vector, and the dequantised vectors replace k and v in `qkv`, so attention over `qkv` (the prefill)
+    sees exactly what the cache holds."""
     nq, nkv, d = int(nq), int(nkv), int(head_dim)
-    _check_cache_args("kv_cache_append", qkv, k_cache, v_cache, nq, nkv, d, {"pos": pos, "rows": rows})
+    _check_cache_args("kv_cache_append", qkv, k_cache, v_cache, nq, nkv, d, {"pos": pos, "rows": rows}, k_scale, v_scale)
     if (cos is None) != (sin is None):
         raise ValueError("kv_cache_append: pass both cos and sin, or neither")
     if cos is not None and (cos.dim() != 2 or cos.shape[1] != d // 2 or cos.shape != sin.shape):
@@ -547,8 +577,11 @@ def kv_cache_append(qkv, k_cache, v_cache, pos, rows, nq, nkv, head_dim, cos=Non
     pos, rows = pos.long(), rows.to(torch.int32)
     if _decode_kernels(qkv, nq, nq, d):  # the append has no group-size limit
         e = torch.empty(0, device=qkv.device)
-        ops.kv_cache_append_(qkv, k_cache, v_cache, e if cos is None else cos, e if sin is None else sin,
-                             pos.contiguous(), rows.contiguous(), nq, nkv, d)
+        tail = (e if cos is None else cos, e if sin is None else sin, pos.contiguous(), rows.contiguous(), nq, nkv, d)
+        if k_scale is None:
+            ops.kv_cache_append_(qkv, k_cache, v_cache, *tail)
+        else:
+            ops.kv_cache_append_fp8_(qkv, k_cache, v_cache, k_scale, v_scale, *tail)
         return qkv
     T, h = qkv.shape[0], d // 2
     ok = (pos >= 0) & (pos < k_cache.shape[2]) & (rows >= 0) & (rows < k_cache.shape[0])
@@ -562,21 +595,33 @@ def kv_cache_append(qkv, k_cache, v_cache, pos, rows, nq, nkv, head_dim, cos=Non
         qkv[:, : (nq + nkv) * d] = torch.where(ok[:, None], rot, qkv[:, : (nq + nkv) * d])
     # boolean selection of the in-range tokens: one host sync, which this fallback path accepts
     r, p = rows.long()[ok], pos[ok]
+    if k_scale is not None:
+        for cache, scales, c0 in ((k_cache, k_scale, nq * d), (v_cache, v_scale, (nq + nkv) * d)):
+            x = qkv[:, c0:c0 + nkv * d].reshape(T, nkv, d)[ok]
+            codes, s = quantize_fp8_rows(x.reshape(-1, d).float())
+            codes, s = codes.reshape(x.shape), s.reshape(x.shape[:2])
+            cache.view(torch.uint8)[r, :, p] = codes.view(torch.uint8)
+            scales[r, :, p] = s
+            qkv[:, c0:c0 + nkv * d][ok] = _dequantized(codes, s, qkv.dtype).reshape(-1, nkv * d)
+        return qkv
     k_cache[r, :, p] = qkv[:, nq * d:(nq + nkv) * d].reshape(T, nkv, d)[ok]
     v_cache[r, :, p] = qkv[:, (nq + nkv) * d:].reshape(T, nkv, d)[ok]
     return qkv
 
 
 @torch.no_grad()
-def decode_attention(qkv, k_cache, v_cache, rows, lens, nq, nkv, head_dim, max_len, scale=None, window=0, splits=0):
+def decode_attention(qkv, k_cache, v_cache, rows, lens, nq, nkv, head_dim, max_len, scale=None, window=0, splits=0,
+                     k_scale=None, v_scale=None):
     """Attention of one query token per sequence against its KV-cache row -> [B, nq * d].
 
     Row b's query heads are read out of the fused `qkv` row b and attend to keys
     [max(0, lens[b] - window), lens[b]) of cache row rows[b] (window 0 = all).  `lens` / `rows` stay on
     the device; `max_len` is a host upper bound of lens, used for the launch plan only.  `splits` > 0
-    overrides the planned split-KV count."""
+    overrides the planned split-KV count.  `k_scale` / `v_scale`: the caches are float8_e4m3fn with one f32
+    scale per key vector (see `kv_cache_append`); the kernel then returns, bit for bit, what it returns on the
+    bf16 cache those stand for."""
     nq, nkv, d = int(nq), int(nkv), int(head_dim)
-    _check_cache_args("decode_attention", qkv, k_cache, v_cache, nq, nkv, d, {"rows": rows, "lens": lens})
+    _check_cache_args("decode_attention", qkv, k_cache, v_cache, nq, nkv, d, {"rows": rows, "lens": lens}, k_scale, v_scale)
     max_len, window, splits = int(max_len), int(window or 0), int(splits)
     if not 0 <= max_len <= k_cache.shape[2]:
         raise ValueError(f"decode_attention: max_len {max_len} outside [0, S_max = {k_cache.shape[2]}]")
@@ -585,8 +630,13 @@ def decode_attention(qkv, k_cache, v_cache, rows, lens, nq, nkv, head_dim, max_l
     if scale is None:
         scale = 1.0 / math.sqrt(d)
     if _decode_kernels(qkv, nq, nkv, d):
-        return ops.decode_attn(qkv, k_cache, v_cache, rows.to(torch.int32).contiguous(), lens.to(torch.int32).contiguous(),
-                               nq, nkv, d, float(scale), max_len, window, splits)
+        rows, lens = rows.to(torch.int32).contiguous(), lens.to(torch.int32).contiguous()
+        if k_scale is not None:
+            return ops.decode_attn_fp8(qkv, k_cache, v_cache, k_scale, v_scale, rows, lens, 1, nq, nkv, d, float(scale),
+                                       max_len, window, splits)
+        return ops.decode_attn(qkv, k_cache, v_cache, rows, lens, nq, nkv, d, float(scale), max_len, window, splits)
+    if k_scale is not None:
+        k_cache, v_cache = _dequantized(k_cache, k_scale, qkv.dtype), _dequantized(v_cache, v_scale, qkv.dtype)
     B, g = qkv.shape[0], nq // nkv
     n = lens.long().clamp(0, max_len)
     r = rows.long()
@@ -608,7 +658,7 @@ def decode_attention(qkv, k_cache, v_cache, rows, lens, nq, nkv, head_dim, max_l
 
 @torch.no_grad()
 def decode_attention_multi(qkv, k_cache, v_cache, rows, lens, q_len, nq, nkv, head_dim, max_len, scale=None, window=0,
-                           splits=0):
+                           splits=0, k_scale=None, v_scale=None):
     """Attention of `q_len` new tokens per sequence against its KV-cache row -> [B * q_len, nq * d]: the verify
     pass of speculative decoding.
 
@@ -617,12 +667,13 @@ def decode_attention_multi(qkv, k_cache, v_cache, rows, lens, q_len, nq, nkv, he
     [max(0, len - window), len) of cache row rows[b]; len <= 0 or a row outside the cache gives a row of zeros.
     Causality among the new tokens is the caller's: it appends them first and passes pos + 1.  `max_len` and
     `splits` as in `decode_attention`.  At window 0 the kernel's output row of a token equals, bit for bit,
-    `decode_attention` of that token alone with the same `max_len` and `splits`."""
+    `decode_attention` of that token alone with the same `max_len` and `splits`.  `k_scale` / `v_scale`: an FP8
+    cache, as in `decode_attention`."""
     q_len, nq, nkv, d = int(q_len), int(nq), int(nkv), int(head_dim)
     if q_len < 1 or qkv.dim() != 2 or qkv.shape[0] % q_len:
         raise ValueError(f"decode_attention_multi: q_len ({q_len}) must be >= 1 and divide the rows of qkv "
                          f"{tuple(qkv.shape)}")
-    _check_cache_args("decode_attention_multi", qkv, k_cache, v_cache, nq, nkv, d, {"lens": lens})
+    _check_cache_args("decode_attention_multi", qkv, k_cache, v_cache, nq, nkv, d, {"lens": lens}, k_scale, v_scale)
     B = qkv.shape[0] // q_len
     if rows.dim() != 1 or rows.numel() != B or rows.dtype not in (torch.int32, torch.int64):
         raise ValueError(f"decode_attention_multi: rows must be an integer tensor [{B}] (one cache row per sequence), "
@@ -635,12 +686,15 @@ def decode_attention_multi(qkv, k_cache, v_cache, rows, lens, q_len, nq, nkv, he
     if scale is None:
         scale = 1.0 / math.sqrt(d)
     if _decode_kernels(qkv, nq, nkv, d):
-        return ops.decode_attn_multi(qkv, k_cache, v_cache, rows.to(torch.int32).contiguous(),
-                                     lens.to(torch.int32).contiguous(), q_len, nq, nkv, d, float(scale), max_len, window,
+        rows, lens = rows.to(torch.int32).contiguous(), lens.to(torch.int32).contiguous()
+        if k_scale is not None:
+            return ops.decode_attn_fp8(qkv, k_cache, v_cache, k_scale, v_scale, rows, lens, q_len, nq, nkv, d,
+                                       float(scale), max_len, window, splits)
+        return ops.decode_attn_multi(qkv, k_cache, v_cache, rows, lens, q_len, nq, nkv, d, float(scale), max_len, window,
                                      splits)
     # decode_attention's composition (the same rule sends it there), one query row per token: masked slots zeroed
     return decode_attention(qkv, k_cache, v_cache, rows.repeat_interleave(q_len), lens, nq, nkv, d, max_len, scale, window,
-                            splits)
+                            splits, k_scale, v_scale)
 
 
 # --------------------------------------------------------------------------------------------

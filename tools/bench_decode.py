@@ -9,7 +9,11 @@ any implementation has to read; q, the output and the split partials are below 1
 is warmed up, the two paths alternate, and each timing covers at least `--min-ms` of device time.
 Needs a GPU: there is no CPU fallback for a timing.
 
-    python tools/bench_decode.py [--md OUT.md]
+--kv-cache fp8 adds the kernel's e4m3 cache format as a third arm, alternated with the bf16 kernel in the same
+process: the same keys quantised per key vector (ops.quantize_fp8_rows), so its bytes are
+2 x B x nkv x len x (D + 4): the codes and one f32 scale per key vector.  --no-composed drops the torch arm.
+
+    python tools/bench_decode.py [--md OUT.md] [--kv-cache fp8] [--no-composed]
 """
 import argparse
 import json
@@ -53,6 +57,8 @@ def main():
     ap.add_argument("--lengths", default=None, help="comma-separated cache lengths instead of 1024,8192,32768")
     ap.add_argument("--true-len", type=int, default=None, help="every sequence is this long while the launch plan is "
                     "made for the cache length (max_len): what planning for a whole length bucket costs")
+    ap.add_argument("--kv-cache", choices=("bf16", "fp8"), default="bf16", help="fp8: also time the kernel on an e4m3 cache")
+    ap.add_argument("--no-composed", action="store_true", help="skip the composed torch arm")
     a = ap.parse_args()
     batches = BATCHES if a.batches is None else tuple(int(v) for v in a.batches.split(","))
     lengths = LENGTHS if a.lengths is None else tuple(int(v) for v in a.lengths.split(","))
@@ -79,18 +85,44 @@ def main():
             def call():
                 return ops.decode_attention(qkv, kc, vc, rows, lens, NQ, NKV, D, L)
 
+            arms = [True] if a.no_composed else [True, False]
+            if a.kv_cache == "fp8":
+                q8 = []
+                for c in (kc, vc):  # one sequence at a time: the quantiser works in f32
+                    codes = torch.empty(c.shape, dtype=torch.float8_e4m3fn, device=dev)
+                    scale = torch.empty(c.shape[:3], dtype=torch.float32, device=dev)
+                    for b in range(B):
+                        cq, sq = ops.quantize_fp8_rows(c[b].reshape(-1, D))
+                        codes[b], scale[b] = cq.reshape(NKV, L, D), sq.reshape(NKV, L)
+                    q8 += [codes, scale]
+                kq, ks, vq, vs = q8
+
+                def call_fp8():
+                    return ops.decode_attention(qkv, kq, vq, rows, lens, NQ, NKV, D, L, k_scale=ks, v_scale=vs)
+
+                arms.append("fp8")
             res, outs = {}, {}
-            for fused in (True, False, True, False):  # alternate; keep the better median of each path
-                functional._DECODE_FUSED = fused
-                outs[fused] = call()
-                t = time_ms(torch, call, a.min_ms)
-                res[fused] = min(res.get(fused, t), t)
+            for arm in arms * 2:  # alternate; keep the better median of each path
+                functional._DECODE_FUSED = arm is not False
+                fn = call_fp8 if arm == "fp8" else call
+                outs[arm] = fn()
+                t = time_ms(torch, fn, a.min_ms)
+                res[arm] = min(res.get(arm, t), t)
             functional._DECODE_FUSED = True
-            diff = (outs[True].float() - outs[False].float()).abs().max().item()
             nbytes = 2 * B * NKV * n_keys * D * 2
-            r = {"batch": B, "len": L, "keys": n_keys, "kernel_us": round(res[True] * 1e3, 1), "composed_us": round(res[False] * 1e3, 1),
-                 "kernel_GBps": round(nbytes / res[True] / 1e6, 1), "composed_GBps": round(nbytes / res[False] / 1e6, 1),
-                 "speedup": round(res[False] / res[True], 2), "max_abs_diff": round(diff, 5)}
+            r = {"batch": B, "len": L, "keys": n_keys, "kernel_us": round(res[True] * 1e3, 1),
+                 "kernel_GBps": round(nbytes / res[True] / 1e6, 1)}
+            if False in res:
+                diff = (outs[True].float() - outs[False].float()).abs().max().item()
+                r.update({"composed_us": round(res[False] * 1e3, 1), "composed_GBps": round(nbytes / res[False] / 1e6, 1),
+                          "speedup": round(res[False] / res[True], 2), "max_abs_diff": round(diff, 5)})
+            if "fp8" in res:
+                nbytes8 = 2 * B * NKV * n_keys * (D + 4)
+                r.update({"fp8_us": round(res["fp8"] * 1e3, 1), "fp8_GBps": round(nbytes8 / res["fp8"] / 1e6, 1),
+                          "bf16_over_fp8": round(res[True] / res["fp8"], 2), "bf16_MB": round(nbytes / 2 ** 20, 1),
+                          "fp8_MB": round(nbytes8 / 2 ** 20, 1),
+                          "fp8_vs_bf16_max_abs_diff": round((outs["fp8"].float() - outs[True].float()).abs().max().item(), 5)})
+                del kq, vq, ks, vs, q8
             print(json.dumps(r), flush=True)
             rows_out.append(r)
             del kc, vc
@@ -99,8 +131,14 @@ def main():
             fp.write("| batch | cache len | kernel µs | composed µs | kernel GB/s (K+V) | composed GB/s | composed / kernel | max abs diff |\n")
             fp.write("|---|---|---|---|---|---|---|---|\n")
             for r in rows_out:
-                fp.write(f"| {r['batch']} | {r['len']} | {r['kernel_us']} | {r['composed_us']} | {r['kernel_GBps']} | "
-                         f"{r['composed_GBps']} | {r['speedup']} | {r['max_abs_diff']} |\n")
+                fp.write(f"| {r['batch']} | {r['len']} | {r['kernel_us']} | {r.get('composed_us')} | {r['kernel_GBps']} | "
+                         f"{r.get('composed_GBps')} | {r.get('speedup')} | {r.get('max_abs_diff')} |\n")
+            if a.kv_cache == "fp8":
+                fp.write("\n| batch | cache len | bf16 MB | fp8 MB | bf16 µs | fp8 µs | bf16 GB/s | fp8 GB/s (codes + scales) | bf16 / fp8 |\n")
+                fp.write("|---|---|---|---|---|---|---|---|---|\n")
+                for r in rows_out:
+                    fp.write(f"| {r['batch']} | {r['len']} | {r['bf16_MB']} | {r['fp8_MB']} | {r['kernel_us']} | {r['fp8_us']} | "
+                             f"{r['kernel_GBps']} | {r['fp8_GBps']} | {r['bf16_over_fp8']} |\n")
 
 
 if __name__ == "__main__":

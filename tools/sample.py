@@ -64,6 +64,8 @@ def main(argv=None):
     ap.add_argument("--linear", choices=("blas", "skinny", "skinny-fp8"), default="blas",
                     help="decode-step projections: hipBLASLt, the skinny-GEMM HIP kernel, or that kernel on weight-only "
                     "FP8 (e4m3, per-row scales) copies of the matrices, quantised at start (at most 16 prompts)")
+    ap.add_argument("--kv-cache", choices=("bf16", "fp8"), default="bf16",
+                    help="fp8: an e4m3 KV cache with one power-of-two scale per key vector, about half the bytes")
     ap.add_argument("--decode", choices=("eager", "graph"), default="eager",
                     help="graph: capture the decode step into one HIP graph per length bucket and replay it (GPU; "
                     "sampling then needs --sampler fused)")
@@ -133,7 +135,7 @@ def main(argv=None):
     t0 = time.perf_counter()
     out = dtg.generate(model, prompts, a.max_new_tokens, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p,
                        eos_token_id=eos, seed=a.seed, min_p=a.min_p, sampler=a.sampler, linear=a.linear, decode=a.decode,
-                       speculate=spec)
+                       speculate=spec, kv_cache=a.kv_cache)
     sync()
     dt = time.perf_counter() - t0
     if spec is not None:
