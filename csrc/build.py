@@ -3,8 +3,9 @@
 
 Every `csrc/kernels/*.hip` file is compiled by `hipcc --offload-arch=gfx950` straight from
 CDNA4 source; `csrc/cpu/*.cpp` (the offload AdamW, packing helpers) and `csrc/comm/*.hip`
-are compiled alongside, and everything is linked against libtorch into
-`lambda-labs_distributed-training-guide_amd/_C.so`, which `dtg.ops` loads with
+(xGMI collectives, the pinned host allocator) are compiled alongside, and everything is
+linked against libtorch into `lambda-labs_distributed-training-guide_amd/_C.so`, which
+`dtg.ops` loads with
 `torch.ops.load_library`.  Operator schemas are declared in Python (`dtg/ops/_schema.py`);
 the objects here only register implementations (`TORCH_LIBRARY_IMPL(dtg, CUDA|CPU, ...)`).
 
@@ -80,7 +81,9 @@ def build(jobs: int | None = None, force: bool = False, verbose: bool = False, o
     # allocator placed the S / dP tiles in the same AGPRs and copied 32-64 accumulator registers
     # out and back (v_accvgpr_read/write) every item -- 96-128 extra VALU per 32-96 MFMAs in
     # the loop (ISA counted with llvm-objdump).  The VGPR form removes all of them, no spills.
-    per_file = {"flash_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]} if per_file_flags else {}
+    # host_mem.hip: built without packed-f32 VALU ops (v_pk_*_f32), as all new HIP code is.
+    per_file = {"flash_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+                "host_mem.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]} if per_file_flags else {}
     srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")) + glob.glob(os.path.join(CSRC, "comm", "*.hip")))
     cpu_srcs = sorted(glob.glob(os.path.join(CSRC, "cpu", "*.cpp")))
     hdr_t = _newest_header()
