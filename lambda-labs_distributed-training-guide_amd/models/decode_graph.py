@@ -20,9 +20,9 @@ What makes the step replayable:
 The first `warmup` steps of a run that has no graph for its bucket yet are real eager steps on the
 capture stream (lazy initialisation, allocator warm-up); the capture itself executes nothing, so the
 cache is not advanced by it.  All work runs on one dedicated stream: the graph is a plain chain of
-kernels.  With linear="skinny" (and "skinny-fp8", whose e4m3 weight copies are static device tensors
-held by this object) every kernel of the step is this project's and deterministic, and the
-captured loop returns the ids of `generate(..., decode="eager", bucketed=True)` bit for bit; with
+kernels.  With linear="skinny" (and "skinny-mfma", which takes up to 64 sequences, and
+"skinny-fp8", whose e4m3 weight copies are static device tensors held by this object) every kernel of the step is this project's and deterministic, and the
+captured loop returns the ids of `generate(..., decode="eager", bucketed=True)` in the same mode bit for bit; with
 linear="blas" hipBLASLt may choose other algorithms under capture and the two agree to rounding.
 """
 from __future__ import annotations

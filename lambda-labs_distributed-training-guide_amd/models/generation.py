@@ -23,7 +23,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .. import ops
-from ..ops.functional import SKINNY_MAX_M
+from ..ops.functional import SKINNY_MAX_M, SKINNY_MFMA_MAX_M
 from .gpt2 import GPT2LMHeadModel
 from .llama import LlamaForCausalLM
 
@@ -85,7 +85,7 @@ class KVCache:
         self.max_len = 0
 
 
-LINEAR_MODES = ("blas", "skinny", "skinny-fp8")
+LINEAR_MODES = ("blas", "skinny", "skinny-fp8", "skinny-mfma")
 KV_CACHE_MODES = ("bf16", "fp8")
 
 
@@ -94,11 +94,18 @@ def _check_kv_cache(kv_cache):
         raise ValueError(f"kv_cache must be one of {KV_CACHE_MODES}, got {kv_cache!r}")
 
 
+def linear_max_rows(linear):
+    """The rows one pass may hold with this `linear` mode: 16 for "skinny" / "skinny-fp8", 64 for "skinny-mfma",
+    None (no limit) for "blas"."""
+    return {"blas": None, "skinny-mfma": SKINNY_MFMA_MAX_M}.get(linear, SKINNY_MAX_M)
+
+
 def _check_linear(linear, n=None):
     if linear not in LINEAR_MODES:
         raise ValueError(f"linear must be one of {LINEAR_MODES}, got {linear!r}")
-    if linear != "blas" and n is not None and n > SKINNY_MAX_M:
-        raise ValueError(f'linear="{linear}" decodes at most {SKINNY_MAX_M} sequences per step, got {n}')
+    limit = linear_max_rows(linear)
+    if limit is not None and n is not None and n > limit:
+        raise ValueError(f'linear="{linear}" decodes at most {limit} sequences per step, got {n}')
 
 
 def _check_fp8(model, linear, fp8, build=False):
@@ -121,7 +128,8 @@ def _projections(model, linear, fp8):
     """The matrix products of one pass through the model, chosen once per call: proj(x, i, name, w, bias) is
     the product with layer i's matrix `w`, which Fp8DecodeWeights calls `name`; mlp(x, i, m) the SwiGLU MLP `m`
     of layer i; head(h) the LM head.  linear="skinny" (a decode step of at most 16 rows): ops.skinny_linear
-    instead of hipBLASLt, gate_up with its SwiGLU epilogue; linear="skinny-fp8": ops.skinny_linear_fp8 on the
+    instead of hipBLASLt, gate_up with its SwiGLU epilogue; linear="skinny-mfma" (at most 64 rows): the same
+    through ops.skinny_linear_mfma; linear="skinny-fp8": ops.skinny_linear_fp8 on the
     e4m3 copies `fp8` (models/quantized.py; the bf16 kernel for a head without a copy).  linear="blas" with
     `fp8` is the prefill of an FP8 run: hipBLASLt on the bf16 matrices the copies stand for (`fp8.dequantized`,
     made where they are used and dropped), so the keys and values the prompt leaves in the cache belong to the
@@ -141,9 +149,11 @@ def _projections(model, linear, fp8):
         def head(h):
             return ops.linear(h, fp8.dequantized("lm_head") if fp8_head else model.lm_head_weight())
     else:
+        bf16_linear = ops.skinny_linear_mfma if linear == "skinny-mfma" else ops.skinny_linear
+
         def proj(x, i, name, w, bias=None, act=None):
             if fp8 is None:
-                return ops.skinny_linear(x, w, bias, act)
+                return bf16_linear(x, w, bias, act)
             return ops.skinny_linear_fp8(x, *fp8.layer(i, name), bias, act)
 
         def mlp(x, i, m):
@@ -151,7 +161,7 @@ def _projections(model, linear, fp8):
             return proj(h, i, "mlp.down_proj", m.down_proj.weight)
 
         def head(h):
-            return ops.skinny_linear_fp8(h, *fp8.head()) if fp8_head else ops.skinny_linear(h, model.lm_head_weight())
+            return ops.skinny_linear_fp8(h, *fp8.head()) if fp8_head else bf16_linear(h, model.lm_head_weight())
     return proj, mlp, head
 
 
@@ -265,7 +275,8 @@ def decode_step(model, tokens: torch.Tensor, cache: KVCache, rows: Optional[Sequ
     it at the row's current length and returns the next-token logits [n, V].
 
     linear="skinny": the five projections of the step (qkv, o, gate_up with its SwiGLU, down, LM head)
-    run in `ops.skinny_linear` (at most 16 sequences); linear="skinny-fp8": in `ops.skinny_linear_fp8` on
+    run in `ops.skinny_linear` (at most 16 sequences); linear="skinny-mfma": in `ops.skinny_linear_mfma` (at
+    most 64); linear="skinny-fp8": in `ops.skinny_linear_fp8` on
     the e4m3 weight copies `fp8` (an `Fp8DecodeWeights` of this model, required).  `plan_len`: the host length the attention's
     launch plan is made for, cache.max_len + 1 <= plan_len <= S_max (default cache.max_len + 1, the
     tightest); a captured step is planned for its whole length bucket, and an eager step given the same
@@ -300,8 +311,8 @@ def extend_step(model, tokens: torch.Tensor, q_valid: torch.Tensor, cache: KVCac
     Built from device tensors only (`q_valid` is not read on the host).  Does NOT advance cache.lens or
     cache.max_len: the caller does, by the number of tokens it accepts; what it rejects stays past lens and is
     overwritten later.  `plan_len` as in `decode_step` (default: cache.max_len + Q, capped at S_max); it must
-    cover the largest length the pass attends.  linear="skinny" / "skinny-fp8" run all n * Q rows in one
-    skinny GEMM, so n * Q may not exceed its row limit."""
+    cover the largest length the pass attends.  linear="skinny" / "skinny-fp8" / "skinny-mfma" run all n * Q rows in
+    one skinny GEMM, so n * Q may not exceed the mode's row limit (`linear_max_rows`: 16, 16, 64)."""
     _check_model(model)
     dev = cache.lens.device
     if tokens.dim() != 2 or tokens.shape[1] < 1:
@@ -310,8 +321,9 @@ def extend_step(model, tokens: torch.Tensor, q_valid: torch.Tensor, cache: KVCac
     if q_valid.dim() != 1 or q_valid.numel() != n:
         raise ValueError(f"extend_step: q_valid must be [{n}], got {tuple(q_valid.shape)}")
     _check_linear(linear)
-    if linear != "blas" and n * Q > SKINNY_MAX_M:
-        raise ValueError(f'extend_step: linear="{linear}" takes at most {SKINNY_MAX_M} rows per pass, got '
+    limit = linear_max_rows(linear)
+    if limit is not None and n * Q > limit:
+        raise ValueError(f'extend_step: linear="{linear}" takes at most {limit} rows per pass, got '
                          f"{n} sequences x {Q} tokens = {n * Q}")
     fp8 = _check_fp8(model, linear, fp8)
     if cache.max_len + 1 > cache.s_max:
@@ -404,20 +416,23 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
 
     linear="skinny": the decode steps' projections run in `ops.skinny_linear` (at most 16 prompts; the
     prefill keeps hipBLASLt).  linear="skinny-fp8": they run in `ops.skinny_linear_fp8` on weight-only FP8
-    copies of the matrices (models/quantized.py).  The model is not modified and keeps its bf16 weights; the
+    copies of the matrices (models/quantized.py).  linear="skinny-mfma": they run in `ops.skinny_linear_mfma`,
+    the bf16 product on the matrix pipe, for up to 64 prompts (where it beats "skinny" and hipBLASLt:
+    profiles/r8/skinny_mfma/README.md).  The model is not modified and keeps its bf16 weights; the
     prefill stays hipBLASLt in bf16 on the dequantised matrices, so the whole call computes one quantised
     model.  `fp8` is an `Fp8DecodeWeights` of this model to reuse, None quantises the model for this call.  decode="graph" (GPU only): the decode loop is captured into one HIP graph
     per length bucket (`decode_bucket`) and replayed, see models/decode_graph.py; sampling then needs
     sampler="fused", whose draw counter lives on the device.  `decode` may also be a `GraphedDecode`
     built for this model, batch size and `s_max`: its graphs and cache are reused.  decode="eager" with
     `bucketed=True` runs the eager loop with the launch plans of the captured one (plan_len = the
-    bucket): with linear="skinny" the two loops return the same ids bit for bit.
+    bucket): with linear="skinny" (or any other skinny mode) the two loops return the same ids bit for bit.  Every
+    bit-for-bit promise here holds within one `linear` mode, never across modes: they sum in different orders.
 
     `speculate` (a `Speculative`, models/speculative.py; None leaves everything above as it is): speculative
     decoding with exact-match verification.  Every step runs the last accepted id and up to k - 1 drafted ids
     of each row through one `extend_step` and keeps the drafted ids that equal the model's own id of their
     position.  Eager only; sampling needs sampler="fused".  With linear="skinny" / "skinny-fp8" (at most
-    SKINNY_MAX_M rows: prompts x k) the ids are those of the plain loop planned for the same length, bit for bit.
+    16 rows: prompts x k) or "skinny-mfma" (at most 64) the ids are those of the plain loop planned for the same length, bit for bit.
 
     kv_cache="fp8": the KV cache is e4m3 with one power-of-two scale per key vector (`KVCache`), about half the
     bytes; it composes with every `linear`, `decode` and `speculate` choice, and the bitwise promises above hold

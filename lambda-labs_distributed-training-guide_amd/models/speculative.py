@@ -5,10 +5,11 @@ the model over n * k rows, `ops.decode_attention_multi` for the attention), comp
 of those positions -- argmax, or the fused sampler's draw with the row's stream and step = the index of the id
 in the row's output -- and accepts a drafted id if and only if it equals the id the model produced for the
 position before.  A row therefore emits the ids the plain loop would have emitted, a + 1 of them per step (a =
-the accepted drafts): not ids "distributed like" them.  With linear="skinny" / "skinny-fp8" every kernel on the
-path computes a row's result independently of the other rows of the launch (skinny GEMM, norms, RoPE, the
-append, the verify attention against `decode_attn`, the sampler), so the ids equal, bit for bit, those of the
-eager loop planned for the same length.  hipBLASLt (linear="blas"), the CPU operators and a sliding window
+the accepted drafts): not ids "distributed like" them.  With linear="skinny" / "skinny-fp8" (prompts x k <= 16 rows)
+or "skinny-mfma" (<= 64 rows, e.g. 8 prompts at k = 4) every kernel on the path computes a row's result
+independently of the other rows of the launch (skinny GEMM, norms, RoPE, the append, the verify attention against `decode_attn`, the sampler), so the ids equal, bit for bit, those of the
+eager loop planned for the same length and run in the same `linear` mode (the modes sum in different orders and
+agree with each other only to rounding).  hipBLASLt (linear="blas"), the CPU operators and a sliding window
 promise no such independence; there the ids agree up to rounding ties.
 
 Launch plan: every verify pass is planned for one length, decode_bucket(longest prompt + max_new_tokens,
@@ -28,7 +29,6 @@ from typing import List, Sequence
 import torch
 
 from .. import ops
-from ..ops.functional import SKINNY_MAX_M
 
 
 class NgramDrafter:
@@ -85,9 +85,12 @@ def check_speculate(spec, n, linear, graphed, sampler, temperature):
     if sampler == "torch" and not isinstance(temperature, (list, tuple, torch.Tensor)) and temperature > 0.0:
         raise ValueError('generate: speculative decoding with temperature > 0 needs sampler="fused" (its draw is a '
                          "function of seed, stream and step, so every drafted position can be verified)")
-    if linear != "blas" and n * spec.k > SKINNY_MAX_M:
+    from .generation import linear_max_rows
+
+    limit = linear_max_rows(linear)
+    if limit is not None and n * spec.k > limit:
         raise ValueError(f'generate: linear="{linear}" with speculation verifies prompts x k = {n} x {spec.k} = '
-                         f"{n * spec.k} rows per step, over the skinny limit of {SKINNY_MAX_M}")
+                         f"{n * spec.k} rows per step, over the skinny limit of {limit}")
 
 
 def _accept(drafts: Sequence[int], target: Sequence[int]) -> int:

@@ -36,6 +36,7 @@ from .functional import (  # noqa: E402
     sample_logits,
     skinny_linear,
     skinny_linear_fp8,
+    skinny_linear_mfma,
     swiglu,
     swiglu_mlp,
     vocab_parallel_fused_linear_cross_entropy,
@@ -65,4 +66,5 @@ __all__ = [
     "rope_tables", "swiglu", "swiglu_mlp", "vocab_parallel_fused_linear_cross_entropy", "route_param_grad", "adamw_step",
     "fa_tuning", "layer_norm", "dropout_add_layer_norm", "gelu_mlp", "qk_norm_rope", "kv_cache_append", "decode_attention",
     "sample_logits", "skinny_linear", "skinny_linear_fp8", "quantize_fp8_rows", "decode_attention_multi",
+    "skinny_linear_mfma",
 ]

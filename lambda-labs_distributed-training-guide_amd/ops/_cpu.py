@@ -232,17 +232,18 @@ def swiglu_fwd(gu):
 
 
 SKINNY_MAX_M = 16  # rows of x the skinny kernels are instantiated for (kSkinnyMaxM); imported where it is needed
+SKINNY_MFMA_MAX_M = 64  # rows of x the MFMA skinny kernel takes (kMfmaMaxM)
 
 
-def _skinny_check(name, x, w, act, chunk, w_layout):
-    """The refusals the two skinny operators share; `chunk` = weights per 16-B load, `w_layout` the operator's
-    own message for the weight matrix."""
+def _skinny_check(name, x, w, act, chunk, w_layout, max_m=SKINNY_MAX_M):
+    """The refusals the skinny operators share; `chunk` = the unit of K (weights per 16-B load, or the MFMA's
+    slab), `w_layout` the operator's own message for the weight matrix, `max_m` its row limit."""
     if x.dtype != torch.bfloat16:
         raise RuntimeError(f"{name}: x must be a bf16 tensor")
     if act not in (0, 1):
         raise RuntimeError(f"{name}: act must be 0 (none) or 1 (SwiGLU)")
-    if x.dim() != 2 or not 1 <= x.shape[0] <= SKINNY_MAX_M:
-        raise RuntimeError(f"{name}: x must be [M, K] with 1 <= M <= {SKINNY_MAX_M}")
+    if x.dim() != 2 or not 1 <= x.shape[0] <= max_m:
+        raise RuntimeError(f"{name}: x must be [M, K] with 1 <= M <= {max_m}")
     if x.shape[1] % chunk:
         raise RuntimeError(f"{name}: K must be a multiple of {chunk}")
     if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
@@ -271,6 +272,16 @@ def skinny_linear(x, w, bias, act=0):
     if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
         raise RuntimeError(f"{name}: x and w must be bf16 tensors")
     _skinny_check(name, x, w, act, 8, "w must be a contiguous [N, K] on x's device")
+    return _skinny_tail(name, x.float() @ w.float().t(), bias, act, x.dtype)
+
+
+def skinny_linear_mfma(x, w, bias, act=0):
+    """skinny_linear at 1 <= M <= 64 rows and K % 32 == 0 (csrc/kernels/skinny_mfma.hip): an f32 matmul, one
+    rounding, the same act.  Refuses what the kernel refuses."""
+    name = "dtg: skinny_linear_mfma"
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        raise RuntimeError(f"{name}: x and w must be bf16 tensors")
+    _skinny_check(name, x, w, act, 32, "w must be a contiguous 16-B aligned [N, K] on x's device", SKINNY_MFMA_MAX_M)
     return _skinny_tail(name, x.float() @ w.float().t(), bias, act, x.dtype)
 
 
@@ -916,7 +927,7 @@ for _name, _fn in list(globals().items()):
         "flash_attn_varlen_bwd", "flash_attn_fwd_drop", "flash_attn_bwd_drop", "flash_attn_bwd_qkv_drop", "philox_rng",
         "flash_attn_bwd_qkv_rope", "flash_attn_tuning", "layernorm_fwd", "dropout_add_layernorm_fwd", "layernorm_bwd",
         "gelu_fwd", "gelu_bwd", "gelu_bwd_t", "qk_norm_rope_fwd_", "qk_norm_rope_bwd_", "kv_cache_append_", "decode_attn",
-        "sample_logits", "skinny_linear", "skinny_linear_fp8", "decode_attn_multi",
+        "sample_logits", "skinny_linear", "skinny_linear_fp8", "decode_attn_multi", "skinny_linear_mfma",
         "kv_cache_append_fp8_", "decode_attn_fp8",
     ):
         LIB.impl(_name, _fn, "CPU")

@@ -73,6 +73,9 @@ _DEFS = [
     # the same with weight-only FP8 (the same kernel, its e4m3 weight format): wq float8_e4m3fn (OCP) [N, K]
     # contiguous, K % 16 == 0, scale f32 [N] (one per weight row): y = (x @ float(wq)^T) * scale (+ bias)
     "skinny_linear_fp8(Tensor x, Tensor wq, Tensor scale, Tensor? bias, int act=0) -> Tensor",
+    # the bf16 product on the matrix pipe for 1 <= M <= 64 rows (csrc/kernels/skinny_mfma.hip): K % 32 == 0, w
+    # contiguous and 16-B aligned; the same act and the same promise that a row does not depend on the others
+    "skinny_linear_mfma(Tensor x, Tensor w, Tensor? bias, int act=0) -> Tensor",
     "swiglu_fwd(Tensor gu) -> Tensor",
     "swiglu_bwd(Tensor dh, Tensor gu) -> Tensor",
     "swiglu_bwd_t(Tensor dh, Tensor gu) -> (Tensor, Tensor, Tensor)",

@@ -12,7 +12,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from . import grad_routing as _gr
-from ._cpu import SKINNY_MAX_M
+from ._cpu import SKINNY_MAX_M, SKINNY_MFMA_MAX_M
 from .grad_routing import route_embedding_grad, route_param_grad, route_weight_grad_mm
 
 ops = torch.ops.dtg
@@ -808,15 +808,15 @@ def swiglu(gu):
 _SKINNY_FUSED = os.environ.get("DTG_SKINNY_FUSED", "1") == "1"
 
 
-def _skinny_args(name, x, w, b, act, wname="w"):
-    """What skinny_linear and skinny_linear_fp8 (`name`) share in argument handling; returns act as 0 / 1 and
-    the bias as [N] or None."""
+def _skinny_args(name, x, w, b, act, wname="w", max_m=SKINNY_MAX_M):
+    """What the skinny operators (`name`, of at most `max_m` rows) share in argument handling; returns act as
+    0 / 1 and the bias as [N] or None."""
     if act not in (None, 0, 1, "swiglu"):
         raise ValueError(f"{name}: act must be None or 'swiglu', got {act!r}")
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
         raise ValueError(f"{name}: x [M, K] and {wname} [N, K] do not match: {tuple(x.shape)}, {tuple(w.shape)}")
-    if x.shape[0] > SKINNY_MAX_M:
-        raise ValueError(f"{name}: M = {x.shape[0]} rows exceed the kernel's limit of {SKINNY_MAX_M}")
+    if x.shape[0] > max_m:
+        raise ValueError(f"{name}: M = {x.shape[0]} rows exceed the kernel's limit of {max_m}")
     act = 1 if act in (1, "swiglu") else 0
     if act and w.shape[0] % 2:
         raise ValueError(f"{name}: the SwiGLU epilogue needs an even N, got {w.shape[0]}")
@@ -845,6 +845,20 @@ def skinny_linear(x, w, b=None, act=None):
     if x.is_cuda and not (_SKINNY_FUSED and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16):
         return _skinny_composed_tail(torch.mm(x, w.t()) if b is None else torch.addmm(b, x, w.t()), act)
     return ops.skinny_linear(x, w, b, act)
+
+
+@torch.no_grad()
+def skinny_linear_mfma(x, w, b=None, act=None):
+    """`skinny_linear` for 1 <= M <= 64 rows of x [M, K], K % 32 == 0: the weights are streamed once into
+    v_mfma_f32_16x16x32_bf16 instead of fmaf (csrc/kernels/skinny_mfma.hip).  Same arguments, same `act`
+    (bitwise `swiglu(skinny_linear_mfma(x, w, b))`), and the same promise: f32 accumulation in an order that
+    depends on K alone, so a row's result is the same alone and inside any batch of up to 64 rows.  The order
+    is not that of `skinny_linear`: the two agree to rounding, not bit for bit.  Which to pick at which M:
+    profiles/r8/skinny_mfma/README.md."""
+    act, b = _skinny_args("skinny_linear_mfma", x, w, b, act, max_m=SKINNY_MFMA_MAX_M)
+    if x.is_cuda and not (_SKINNY_FUSED and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16):
+        return _skinny_composed_tail(torch.mm(x, w.t()) if b is None else torch.addmm(b, x, w.t()), act)
+    return ops.skinny_linear_mfma(x, w, b, act)
 
 
 # --------------------------------------------------------------------------------------------

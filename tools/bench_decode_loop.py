@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""The decode loop of dtg.generate in its six forms -- projections in hipBLASLt, in the skinny-GEMM kernel
-or in the weight-only FP8 skinny-GEMM kernel, the loop eager or captured into HIP graphs -- on random-init
-Qwen3-0.6B and Llama-3.2-1B, batch 1 and 8, a 16-token prompt and 256 new tokens, greedy.  The FP8 copies are
+"""The decode loop of dtg.generate in its eight forms -- projections in hipBLASLt, in the skinny-GEMM kernel,
+in the weight-only FP8 skinny-GEMM kernel or in the MFMA skinny-GEMM kernel, the loop eager or captured into
+HIP graphs -- on random-init Qwen3-0.6B and Llama-3.2-1B, batch 1 and 8 (--batches; an arm is left out where
+the batch exceeds its mode's row limit), a 16-token prompt and 256 new tokens, greedy.  The FP8 copies are
 quantised once per model, outside every clock; a step reads every matrix once, and both models' matrices
 (0.6-2.5 GB in either format) exceed the 256 MB Infinity Cache, so no arm re-reads its weights from a cache.
 
@@ -28,7 +29,7 @@ MODELS = ("qwen3-0.6b", "llama-3.2-1b")
 BATCHES = (1, 8)
 PROMPT, NEW, WARM = 16, 256, 8
 ARMS = [("blas", "eager"), ("skinny", "eager"), ("skinny-fp8", "eager"), ("blas", "graph"), ("skinny", "graph"),
-        ("skinny-fp8", "graph")]
+        ("skinny-fp8", "graph"), ("skinny-mfma", "eager"), ("skinny-mfma", "graph")]
 
 
 def run_arm(torch, model, prompts, linear, decode, s_max, fp8=None):
@@ -75,6 +76,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--models", default=",".join(MODELS))
     ap.add_argument("--md", default=None)
+    ap.add_argument("--batches", default=",".join(map(str, BATCHES)))
     a = ap.parse_args()
     import torch
 
@@ -82,6 +84,7 @@ def main():
         raise SystemExit("bench_decode_loop: needs a GPU")
     import dtg  # noqa: F401
     from dtg.models import Fp8DecodeWeights, build_model, resolve_config
+    from dtg.models.generation import linear_max_rows
 
     dev = torch.device("cuda:0")
     rows = []
@@ -90,28 +93,29 @@ def main():
         torch.manual_seed(0)
         model = build_model(cfg, device=dev).eval()
         fp8 = Fp8DecodeWeights(model)
-        for n in BATCHES:
+        for n in map(int, a.batches.split(",")):
+            arms = [arm for arm in ARMS if n <= (linear_max_rows(arm[0]) or n)]
             g = torch.Generator().manual_seed(n)
             prompts = [torch.randint(0, cfg.vocab_size, (PROMPT,), generator=g) for _ in range(n)]
             s_max = PROMPT + NEW
-            res = {arm: [] for arm in ARMS}
-            cap = {arm: 0.0 for arm in ARMS}
+            res = {arm: [] for arm in arms}
+            cap = {arm: 0.0 for arm in arms}
             ids = {}
             with torch.no_grad():
                 for _ in range(a.rounds):
-                    for arm in ARMS:
+                    for arm in arms:
                         tps, c, first = run_arm(torch, model, prompts, arm[0], arm[1], s_max, fp8)
                         res[arm].append(tps)
                         cap[arm] = max(cap[arm], c)
                         ids[arm] = first
             base = sorted(res[("blas", "eager")])[len(res[("blas", "eager")]) // 2]
-            for arm in ARMS:
+            for arm in arms:
                 v = sorted(res[arm])
                 med = v[len(v) // 2]
                 r = {"model": name, "batch": n, "linear": arm[0], "decode": arm[1], "tokens_per_s": round(med, 1),
                      "ms_per_step": round(1e3 * n / med, 3), "spread_pct": round(100 * (v[-1] - v[0]) / med, 1),
                      "vs_baseline": round(med / base, 2), "capture_s": round(cap[arm], 3),
-                     "ids_equal_skinny_eager": bool(torch.equal(ids[arm], ids[("skinny", "eager")]))}
+                     "ids_equal_eager_same_linear": bool(torch.equal(ids[arm], ids[(arm[0], "eager")]))}
                 print(json.dumps(r), flush=True)
                 rows.append(r)
         del model, fp8

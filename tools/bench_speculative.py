@@ -2,15 +2,16 @@
 """Speculative decoding (generate(..., speculate=...)) against the plain eager loop, and the verify attention
 kernel (ops.decode_attention_multi) against Q launches of ops.decode_attention, in one process.
 
-Loop: tokens / s of `generate` at batch 1 and 4 on Qwen3-0.6B and a Llama-3.2-1B-shaped model (random init),
-linear = blas / skinny / skinny-fp8, greedy, for the plain loop and for the speculative loop under three drafters:
+Loop: tokens / s of `generate` at batch 1 and 4 (--batches) on Qwen3-0.6B and a Llama-3.2-1B-shaped model (random
+init), linear = blas / skinny / skinny-fp8 / skinny-mfma (a mode is left out where batch x k exceeds its row
+limit), greedy, for the plain loop and for the speculative loop under three drafters:
   oracle  proposes the plain run's own ids: everything is accepted, the ceiling of the mode;
   wrong   proposes ids that are never right: one id per verify pass, the floor (the cost of a wasted verify);
   ngram   the built-in prompt-lookup drafter on a prompt that repeats itself (a random-init model does not
           repeat its prompt, so this mostly shows the drafter's host cost).
 Every run is timed between HIP events around the whole call (device synchronised), after one warm-up call of
 the same kind; the best of `--rounds` is kept.  The ids of every speculative run are compared with the plain
-run's (linear = skinny / skinny-fp8: they must be equal).
+run's (every skinny mode: they must be equal).
 
 Kernel: Llama-3-8B head shape (nq 32, nkv 8, D 128), time per call from HIP events as tools/bench_decode.py
 takes it (warm-up, >= --min-ms per round, median of 3).  Needs a GPU.
@@ -54,6 +55,7 @@ def main():
     ap.add_argument("--min-ms", type=float, default=100.0)
     ap.add_argument("--models", default=",".join(MODELS))
     ap.add_argument("--md", default=None, help="also write the tables as markdown here")
+    ap.add_argument("--batches", default="1,4")
     a = ap.parse_args()
     import torch
 
@@ -62,6 +64,7 @@ def main():
     import dtg  # noqa: F401
     from dtg import ops
     from dtg.models import Fp8DecodeWeights, Speculative, build_model, generate, resolve_config
+    from dtg.models.generation import linear_max_rows
 
     dev = torch.device("cuda:0")
 
@@ -86,13 +89,15 @@ def main():
         torch.manual_seed(0)
         model = build_model(cfg, device=dev).eval()
         fp8_w = Fp8DecodeWeights(model)
-        for batch in (1, 4):
+        for batch in map(int, a.batches.split(",")):
             g = torch.Generator().manual_seed(batch)
             piece = torch.randint(0, cfg.vocab_size, (a.prompt_len // 4,), generator=g)
             prompts = {"random": [torch.randint(0, cfg.vocab_size, (a.prompt_len,), generator=g) for _ in range(batch)],
                        "repeat": [piece.roll(i).repeat(4) for i in range(batch)]}
             s_max = a.prompt_len + a.new
-            for linear in ("blas", "skinny", "skinny-fp8"):
+            for linear in ("blas", "skinny", "skinny-fp8", "skinny-mfma"):
+                if batch * a.k > (linear_max_rows(linear) or batch * a.k):
+                    continue
                 kw = dict(s_max=s_max, linear=linear, fp8=fp8_w if linear == "skinny-fp8" else None)
                 plain = {}
                 for which, pr in prompts.items():
