@@ -22,6 +22,10 @@ def __getattr__(name):  # `from dtg import generate` without importing torch at 
         from .models.quantized import Fp8DecodeWeights
 
         return Fp8DecodeWeights
+    if name == "Mxfp4DecodeWeights":
+        from .models.quantized import Mxfp4DecodeWeights
+
+        return Mxfp4DecodeWeights
     if name == "Speculative":
         from .models.speculative import Speculative
 

@@ -23,7 +23,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .. import ops
-from ..ops.functional import SKINNY_MAX_M, SKINNY_MFMA_MAX_M
+from ..ops.functional import SKINNY_MAX_M, SKINNY_MFMA_MAX_M, SKINNY_MXFP4_MAX_M
 from .gpt2 import GPT2LMHeadModel
 from .llama import LlamaForCausalLM
 
@@ -85,7 +85,7 @@ class KVCache:
         self.max_len = 0
 
 
-LINEAR_MODES = ("blas", "skinny", "skinny-fp8", "skinny-mfma")
+LINEAR_MODES = ("blas", "skinny", "skinny-fp8", "skinny-mfma", "skinny-mxfp4")
 KV_CACHE_MODES = ("bf16", "fp8")
 
 
@@ -95,9 +95,9 @@ def _check_kv_cache(kv_cache):
 
 
 def linear_max_rows(linear):
-    """The rows one pass may hold with this `linear` mode: 16 for "skinny" / "skinny-fp8", 64 for "skinny-mfma",
-    None (no limit) for "blas"."""
-    return {"blas": None, "skinny-mfma": SKINNY_MFMA_MAX_M}.get(linear, SKINNY_MAX_M)
+    """The rows one pass may hold with this `linear` mode: 16 for "skinny" / "skinny-fp8", 64 for "skinny-mfma" /
+    "skinny-mxfp4", None (no limit) for "blas"."""
+    return {"blas": None, "skinny-mfma": SKINNY_MFMA_MAX_M, "skinny-mxfp4": SKINNY_MXFP4_MAX_M}.get(linear, SKINNY_MAX_M)
 
 
 def _check_linear(linear, n=None):
@@ -108,20 +108,42 @@ def _check_linear(linear, n=None):
         raise ValueError(f'linear="{linear}" decodes at most {limit} sequences per step, got {n}')
 
 
-def _check_fp8(model, linear, fp8, build=False):
-    """The FP8 weight copies of a linear="skinny-fp8" call: `fp8` as given, built when `build` allows it."""
-    if linear != "skinny-fp8":
-        if fp8 is not None:
-            raise ValueError(f'fp8 weights were given with linear={linear!r}; they need linear="skinny-fp8"')
-        return None
-    if fp8 is None:
-        if not build:
-            raise ValueError('linear="skinny-fp8" needs fp8=Fp8DecodeWeights(model)')
-        from .quantized import Fp8DecodeWeights
+QUANT_MODES = {"skinny-fp8": ("fp8", "Fp8DecodeWeights"), "skinny-mxfp4": ("mxfp4", "Mxfp4DecodeWeights")}
 
-        return Fp8DecodeWeights(model)
-    fp8.check(model)
-    return fp8
+
+def _one_quant(fp8, mxfp4):
+    """The one set of quantised weight copies a call was given (or None): the two formats share one slot."""
+    if fp8 is not None and mxfp4 is not None:
+        raise ValueError("fp8 and mxfp4 weights were both given; a call streams one format")
+    return fp8 if mxfp4 is None else mxfp4
+
+
+def _quant_kw(quant):
+    """`quant` under the public argument of its format, for the calls that pass the shared slot on."""
+    return {} if quant is None else {QUANT_MODES[quant.mode][0]: quant}
+
+
+def _check_quant(model, linear, fp8, mxfp4=None, build=False):
+    """The quantised weight copies of a linear="skinny-fp8" (`fp8`) or linear="skinny-mxfp4" (`mxfp4`) call: as
+    given, built when `build` allows it; None for every other mode, which takes neither argument."""
+    quant = _one_quant(fp8, mxfp4)
+    if linear != "skinny-fp8" and fp8 is not None:
+        raise ValueError(f'fp8 weights were given with linear={linear!r}; they need linear="skinny-fp8"')
+    if linear != "skinny-mxfp4" and mxfp4 is not None:
+        raise ValueError(f'mxfp4 weights were given with linear={linear!r}; they need linear="skinny-mxfp4"')
+    if linear not in QUANT_MODES:
+        return None
+    arg, cls = QUANT_MODES[linear]
+    if quant is None:
+        if not build:
+            raise ValueError(f'linear="{linear}" needs {arg}={cls}(model)')
+        from . import quantized
+
+        return getattr(quantized, cls)(model)
+    if getattr(quant, "mode", linear) != linear:
+        raise ValueError(f"{arg} must be a {cls} of this model, got a {type(quant).__name__}")
+    quant.check(model)
+    return quant
 
 
 def _projections(model, linear, fp8):
@@ -130,8 +152,10 @@ def _projections(model, linear, fp8):
     of layer i; head(h) the LM head.  linear="skinny" (a decode step of at most 16 rows): ops.skinny_linear
     instead of hipBLASLt, gate_up with its SwiGLU epilogue; linear="skinny-mfma" (at most 64 rows): the same
     through ops.skinny_linear_mfma; linear="skinny-fp8": ops.skinny_linear_fp8 on the
-    e4m3 copies `fp8` (models/quantized.py; the bf16 kernel for a head without a copy).  linear="blas" with
-    `fp8` is the prefill of an FP8 run: hipBLASLt on the bf16 matrices the copies stand for (`fp8.dequantized`,
+    e4m3 copies `fp8` (models/quantized.py; the bf16 kernel for a head without a copy); linear="skinny-mxfp4" (at
+    most 64 rows): ops.skinny_linear_mxfp4 on MXFP4 copies, which travel in the same `fp8` slot here and in the
+    functions below (only layer(i, name), head() and dequantized(name) are used).  linear="blas" with
+    `fp8` is the prefill of a quantised run: hipBLASLt on the bf16 matrices the copies stand for (`fp8.dequantized`,
     made where they are used and dropped), so the keys and values the prompt leaves in the cache belong to the
     same quantised model as the decode steps that read them."""
     fp8_head = fp8 is not None and fp8.has_head
@@ -149,19 +173,20 @@ def _projections(model, linear, fp8):
         def head(h):
             return ops.linear(h, fp8.dequantized("lm_head") if fp8_head else model.lm_head_weight())
     else:
-        bf16_linear = ops.skinny_linear_mfma if linear == "skinny-mfma" else ops.skinny_linear
+        bf16_linear = ops.skinny_linear_mfma if linear in ("skinny-mfma", "skinny-mxfp4") else ops.skinny_linear
+        quant_linear = ops.skinny_linear_mxfp4 if linear == "skinny-mxfp4" else ops.skinny_linear_fp8
 
         def proj(x, i, name, w, bias=None, act=None):
             if fp8 is None:
                 return bf16_linear(x, w, bias, act)
-            return ops.skinny_linear_fp8(x, *fp8.layer(i, name), bias, act)
+            return quant_linear(x, *fp8.layer(i, name), bias, act)
 
         def mlp(x, i, m):
             h = proj(x, i, "mlp.gate_up_proj", m.gate_up_proj.weight, act="swiglu")
             return proj(h, i, "mlp.down_proj", m.down_proj.weight)
 
         def head(h):
-            return ops.skinny_linear_fp8(h, *fp8.head()) if fp8_head else bf16_linear(h, model.lm_head_weight())
+            return quant_linear(h, *fp8.head()) if fp8_head else bf16_linear(h, model.lm_head_weight())
     return proj, mlp, head
 
 
@@ -212,14 +237,17 @@ def _rows(cache, n, rows, device):
 
 
 @torch.no_grad()
-def prefill(model, prompts: Sequence[torch.Tensor], cache: KVCache, rows: Optional[Sequence[int]] = None, fp8=None):
+def prefill(model, prompts: Sequence[torch.Tensor], cache: KVCache, rows: Optional[Sequence[int]] = None, fp8=None,
+            mxfp4=None):
     """Run the prompts (1-D id tensors of any lengths >= 1) packed token-major, fill cache rows `rows`
     (default 0..n-1) from position 0 and return the logits [n, V] of each prompt's last token.
 
     `fp8` (an `Fp8DecodeWeights` of this model): the prefill of a linear="skinny-fp8" run.  The GEMMs stay
     hipBLASLt in bf16, on the matrices the e4m3 copies stand for instead of the model's own, so prompt and
-    decode steps see one and the same (quantised) model."""
+    decode steps see one and the same (quantised) model.  `mxfp4` (an `Mxfp4DecodeWeights`): the same for a
+    linear="skinny-mxfp4" run; giving both is an error."""
     _check_model(model)
+    fp8 = _one_quant(fp8, mxfp4)  # from here on the one slot for either format
     if fp8 is not None:
         fp8.check(model)
     lens = [int(p.numel()) for p in prompts]
@@ -270,14 +298,15 @@ def _decode_body(model, tokens, cache, rows_t, plan_len, linear, fp8=None):
 
 @torch.no_grad()
 def decode_step(model, tokens: torch.Tensor, cache: KVCache, rows: Optional[Sequence[int]] = None,
-                linear: str = "blas", plan_len: Optional[int] = None, fp8=None):
+                linear: str = "blas", plan_len: Optional[int] = None, fp8=None, mxfp4=None):
     """One new token per active sequence (`tokens` [n], for cache rows `rows`, default 0..n-1): appends
     it at the row's current length and returns the next-token logits [n, V].
 
     linear="skinny": the five projections of the step (qkv, o, gate_up with its SwiGLU, down, LM head)
     run in `ops.skinny_linear` (at most 16 sequences); linear="skinny-mfma": in `ops.skinny_linear_mfma` (at
     most 64); linear="skinny-fp8": in `ops.skinny_linear_fp8` on
-    the e4m3 weight copies `fp8` (an `Fp8DecodeWeights` of this model, required).  `plan_len`: the host length the attention's
+    the e4m3 weight copies `fp8` (an `Fp8DecodeWeights` of this model, required); linear="skinny-mxfp4": in
+    `ops.skinny_linear_mxfp4` (at most 64) on the MXFP4 copies `mxfp4` (an `Mxfp4DecodeWeights`, required).  `plan_len`: the host length the attention's
     launch plan is made for, cache.max_len + 1 <= plan_len <= S_max (default cache.max_len + 1, the
     tightest); a captured step is planned for its whole length bucket, and an eager step given the same
     `plan_len` runs the same launches."""
@@ -287,7 +316,7 @@ def decode_step(model, tokens: torch.Tensor, cache: KVCache, rows: Optional[Sequ
     dev = cache.lens.device
     tokens = tokens.reshape(-1).to(dev)
     _check_linear(linear, tokens.numel())
-    fp8 = _check_fp8(model, linear, fp8)
+    fp8 = _check_quant(model, linear, fp8, mxfp4)
     max_len = cache.max_len + 1
     if plan_len is None:
         plan_len = max_len
@@ -301,7 +330,7 @@ def decode_step(model, tokens: torch.Tensor, cache: KVCache, rows: Optional[Sequ
 
 @torch.no_grad()
 def extend_step(model, tokens: torch.Tensor, q_valid: torch.Tensor, cache: KVCache, rows: Optional[Sequence[int]] = None,
-                linear: str = "blas", plan_len: Optional[int] = None, fp8=None):
+                linear: str = "blas", plan_len: Optional[int] = None, fp8=None, mxfp4=None):
     """Up to Q new tokens per active sequence in one pass (`tokens` [n, Q] ids, `q_valid` [n]: how many of a
     row's Q are real): the verify pass of speculative decoding.  Token t < q_valid[b] of row b is appended at
     position cache.lens[b] + t and attends the keys up to and including its own (`ops.decode_attention_multi`
@@ -311,8 +340,9 @@ def extend_step(model, tokens: torch.Tensor, q_valid: torch.Tensor, cache: KVCac
     Built from device tensors only (`q_valid` is not read on the host).  Does NOT advance cache.lens or
     cache.max_len: the caller does, by the number of tokens it accepts; what it rejects stays past lens and is
     overwritten later.  `plan_len` as in `decode_step` (default: cache.max_len + Q, capped at S_max); it must
-    cover the largest length the pass attends.  linear="skinny" / "skinny-fp8" / "skinny-mfma" run all n * Q rows in
-    one skinny GEMM, so n * Q may not exceed the mode's row limit (`linear_max_rows`: 16, 16, 64)."""
+    cover the largest length the pass attends.  linear="skinny" / "skinny-fp8" / "skinny-mfma" / "skinny-mxfp4" run all
+    n * Q rows in one skinny GEMM, so n * Q may not exceed the mode's row limit (`linear_max_rows`: 16, 16, 64, 64).
+    `fp8` / `mxfp4` as in `decode_step`."""
     _check_model(model)
     dev = cache.lens.device
     if tokens.dim() != 2 or tokens.shape[1] < 1:
@@ -325,7 +355,7 @@ def extend_step(model, tokens: torch.Tensor, q_valid: torch.Tensor, cache: KVCac
     if limit is not None and n * Q > limit:
         raise ValueError(f'extend_step: linear="{linear}" takes at most {limit} rows per pass, got '
                          f"{n} sequences x {Q} tokens = {n * Q}")
-    fp8 = _check_fp8(model, linear, fp8)
+    fp8 = _check_quant(model, linear, fp8, mxfp4)
     if cache.max_len + 1 > cache.s_max:
         raise ValueError(f"extend_step: the cache is full (S_max = {cache.s_max})")
     if plan_len is None:
@@ -399,7 +429,8 @@ def _fused_params(n, **given):
 def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              top_p: float = 1.0, eos_token_id: Optional[int] = None, seed: int = 0, s_max: Optional[int] = None,
              min_p: float = 0.0, sampler: str = "torch", linear: str = "blas", decode="eager",
-             bucketed: bool = False, fp8=None, speculate=None, kv_cache: str = "bf16") -> List[torch.Tensor]:
+             bucketed: bool = False, fp8=None, speculate=None, kv_cache: str = "bf16",
+             mxfp4=None) -> List[torch.Tensor]:
     """Continue every prompt by up to `max_new_tokens` ids; returns the new ids of each sequence (1-D
     int64 tensors on the CPU), ending with `eos_token_id` where the sequence produced it.
 
@@ -420,7 +451,10 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     the bf16 product on the matrix pipe, for up to 64 prompts (where it beats "skinny" and hipBLASLt:
     profiles/r8/skinny_mfma/README.md).  The model is not modified and keeps its bf16 weights; the
     prefill stays hipBLASLt in bf16 on the dequantised matrices, so the whole call computes one quantised
-    model.  `fp8` is an `Fp8DecodeWeights` of this model to reuse, None quantises the model for this call.  decode="graph" (GPU only): the decode loop is captured into one HIP graph
+    model.  `fp8` is an `Fp8DecodeWeights` of this model to reuse, None quantises the model for this call.
+    linear="skinny-mxfp4": the same arrangement with MXFP4 copies (4.25 bits per weight) in `ops.skinny_linear_mxfp4`,
+    for up to 64 prompts; `mxfp4` is an `Mxfp4DecodeWeights` to reuse, None quantises for this call.  Giving both `fp8`
+    and `mxfp4`, or either with a mode it does not belong to, is an error.  decode="graph" (GPU only): the decode loop is captured into one HIP graph
     per length bucket (`decode_bucket`) and replayed, see models/decode_graph.py; sampling then needs
     sampler="fused", whose draw counter lives on the device.  `decode` may also be a `GraphedDecode`
     built for this model, batch size and `s_max`: its graphs and cache are reused.  decode="eager" with
@@ -445,8 +479,11 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     if sampler not in ("torch", "fused"):
         raise ValueError(f"generate: sampler must be 'torch' or 'fused', got {sampler!r}")
     _check_linear(linear, len(prompts))
+    _one_quant(fp8, mxfp4)
     if linear != "skinny-fp8" and fp8 is not None:
         raise ValueError(f'generate: fp8 weights were given with linear={linear!r}; they need linear="skinny-fp8"')
+    if linear != "skinny-mxfp4" and mxfp4 is not None:
+        raise ValueError(f'generate: mxfp4 weights were given with linear={linear!r}; they need linear="skinny-mxfp4"')
     graphed = not isinstance(decode, str)
     if not graphed and decode not in ("eager", "graph"):
         raise ValueError(f"generate: decode must be 'eager', 'graph' or a GraphedDecode, got {decode!r}")
@@ -490,17 +527,19 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
         from .decode_graph import GraphedDecode
 
         gd = decode if isinstance(decode, GraphedDecode) else GraphedDecode(model, n, s_max, linear=linear, fp8=fp8,
-                                                                            kv_cache=kv_cache)
+                                                                            kv_cache=kv_cache, mxfp4=mxfp4)
         if fp8 is not None and gd.fp8 is not fp8:
             raise ValueError("generate: the GraphedDecode was captured with other fp8 weights")
+        if mxfp4 is not None and gd.mxfp4 is not mxfp4:
+            raise ValueError("generate: the GraphedDecode was captured with other mxfp4 weights")
         if gd.cache.kv_cache != kv_cache:
             raise ValueError(f"generate: the GraphedDecode holds a {gd.cache.kv_cache} cache, kv_cache={kv_cache!r} was asked for")
         return gd.run(prompts, max_new_tokens, fused, seed, eos_token_id, s_max=s_max, linear=linear)
-    fp8 = _check_fp8(model, linear, fp8, build=True)
+    quant = _check_quant(model, linear, fp8, mxfp4, build=True)  # the one slot for either format
     if speculate is not None:
         from .speculative import speculative_loop
 
-        return speculative_loop(model, prompts, max_new_tokens, speculate, fused, seed, eos_token_id, s_max, linear, fp8,
+        return speculative_loop(model, prompts, max_new_tokens, speculate, fused, seed, eos_token_id, s_max, linear, quant,
                                 kv_cache)
     gen = None
     if fused is not None:
@@ -515,7 +554,7 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     out = torch.zeros(n, max_new_tokens, dtype=torch.long, device=dev)
     count = torch.zeros(n, dtype=torch.long, device=dev)  # ids kept per sequence
     done = torch.zeros(n, dtype=torch.bool, device=dev)
-    logits = prefill(model, prompts, cache, fp8=fp8)
+    logits = prefill(model, prompts, cache, **_quant_kw(quant))
     for step in range(max_new_tokens):
         if fused is not None:
             nxt, _ = ops.sample_logits(logits, seed=int(seed), stream=stream, step=step_t, **fused)
@@ -530,6 +569,6 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
                 break
         if step + 1 < max_new_tokens:
             plan_len = decode_bucket(cache.max_len + 1, s_max) if bucketed else None
-            logits = decode_step(model, nxt, cache, linear=linear, plan_len=plan_len, fp8=fp8)
+            logits = decode_step(model, nxt, cache, linear=linear, plan_len=plan_len, **_quant_kw(quant))
     out, count = out.cpu(), count.tolist()
     return [out[i, : count[i]].clone() for i in range(n)]

@@ -13,6 +13,11 @@ tiny test models: logit error 0.20-0.27 against 0.07-0.09 for either model alone
 
 With the default power-of-two scales float(wq) * scale is exactly representable in bf16, so the quantised
 model is exactly some bf16 model: `dequantized(name)` returns that model's matrix.
+
+`Mxfp4DecodeWeights` is the same arrangement at 4.25 bits per weight: OCP microscaling FP4 (e2m1 codes, one e8m0
+power-of-two scale per 32 elements of a row, `ops.quantize_mxfp4_rows`), streamed by `ops.skinny_linear_mxfp4`
+with linear="skinny-mxfp4" for up to 64 rows per step.  A code times a power of two is a bf16 value, so that model
+too is exactly some bf16 model, and its prefill runs on `dequantized(name)` for the same reason.
 """
 from __future__ import annotations
 
@@ -31,6 +36,8 @@ class Fp8DecodeWeights:
     """(wq, scale) of every layer's qkv_proj, o_proj, gate_up_proj and down_proj, and with `head=True` of the
     LM head (for tied embeddings a quantised copy of the embedding matrix; the lookup itself stays bf16).
     Names are the modules' paths: "layers.0.self_attn.qkv_proj", ..., "lm_head"."""
+
+    mode = "skinny-fp8"  # the `linear` mode that streams these copies
 
     def __init__(self, model, head: bool = True, pow2: bool = True):
         _check_model(model)
@@ -74,3 +81,31 @@ class Fp8DecodeWeights:
         """The copies belong to a model of this shape on this device."""
         if self.num_layers != len(model.layers) or self.device != model.embed_tokens.weight.device:
             raise ValueError("Fp8DecodeWeights: built for another model or device")
+
+
+class Mxfp4DecodeWeights(Fp8DecodeWeights):
+    """The same matrices as MXFP4 (`ops.quantize_mxfp4_rows`): (wq uint8 [N, K / 2], scales uint8 [N, K / 32]), 4.25
+    bits per weight, streamed by `ops.skinny_linear_mxfp4` with linear="skinny-mxfp4" (up to 64 rows per step).
+    The interface and the reasoning are those of `Fp8DecodeWeights`: the copies live beside the untouched model,
+    `dequantized(name)` is exact in bf16, and the prefill runs hipBLASLt on it.  Every matrix needs K % 32 == 0."""
+
+    mode = "skinny-mxfp4"
+
+    def __init__(self, model, head: bool = True):
+        _check_model(model)
+        self.tensors = {}
+        for i, layer in enumerate(model.layers):
+            for name in LAYER_MATRICES:
+                self.tensors[f"layers.{i}.{name}"] = ops.quantize_mxfp4_rows(layer.get_submodule(name).weight.detach())
+        if head:
+            self.tensors[HEAD] = ops.quantize_mxfp4_rows(model.lm_head_weight().detach())
+        self.num_layers = len(model.layers)
+        self.device = model.embed_tokens.weight.device
+
+    def dequantized(self, name: str) -> torch.Tensor:
+        """The bf16 matrix the codes and block scales stand for (exact)."""
+        return ops.dequantize_mxfp4(*self.tensors[name])
+
+    def check(self, model):
+        if self.num_layers != len(model.layers) or self.device != model.embed_tokens.weight.device:
+            raise ValueError("Mxfp4DecodeWeights: built for another model or device")

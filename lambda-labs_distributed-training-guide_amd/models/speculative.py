@@ -6,7 +6,7 @@ of those positions -- argmax, or the fused sampler's draw with the row's stream 
 in the row's output -- and accepts a drafted id if and only if it equals the id the model produced for the
 position before.  A row therefore emits the ids the plain loop would have emitted, a + 1 of them per step (a =
 the accepted drafts): not ids "distributed like" them.  With linear="skinny" / "skinny-fp8" (prompts x k <= 16 rows)
-or "skinny-mfma" (<= 64 rows, e.g. 8 prompts at k = 4) every kernel on the path computes a row's result
+or "skinny-mfma" / "skinny-mxfp4" (<= 64 rows, e.g. 8 prompts at k = 4) every kernel on the path computes a row's result
 independently of the other rows of the launch (skinny GEMM, norms, RoPE, the append, the verify attention against `decode_attn`, the sampler), so the ids equal, bit for bit, those of the
 eager loop planned for the same length and run in the same `linear` mode (the modes sum in different orders and
 agree with each other only to rounding).  hipBLASLt (linear="blas"), the CPU operators and a sliding window
@@ -101,11 +101,11 @@ def _accept(drafts: Sequence[int], target: Sequence[int]) -> int:
     return a
 
 
-def speculative_loop(model, prompts, max_new_tokens, spec, fused, seed, eos_token_id, s_max, linear, fp8,
+def speculative_loop(model, prompts, max_new_tokens, spec, fused, seed, eos_token_id, s_max, linear, quant,
                      kv_cache="bf16"):
     """generate()'s loop under `spec`; arguments as generate() has checked them (`fused`: the per-prompt host lists
-    of the fused sampler's parameters, or None for argmax)."""
-    from .generation import KVCache, decode_bucket, extend_step, prefill
+    of the fused sampler's parameters, or None for argmax; `quant`: the quantised weight copies of the mode, or None)."""
+    from .generation import KVCache, _quant_kw, decode_bucket, extend_step, prefill
 
     n, k = len(prompts), spec.k
     dev = model.embed_tokens.weight.device
@@ -139,7 +139,7 @@ def speculative_loop(model, prompts, max_new_tokens, spec, fused, seed, eos_toke
                 done[b] = True
                 break
 
-    first = target(prefill(model, prompts, cache, fp8=fp8), 1, [0] * n).tolist()
+    first = target(prefill(model, prompts, cache, **_quant_kw(quant)), 1, [0] * n).tolist()
     for b in range(n):
         emit(b, first[b:b + 1])
     while not all(done):
@@ -154,7 +154,7 @@ def speculative_loop(model, prompts, max_new_tokens, spec, fused, seed, eos_toke
         q_valid = [0 if done[b] else 1 + len(drafts[b]) for b in range(n)]
         logits = extend_step(model, torch.tensor(tokens, dtype=torch.long, device=dev),
                              torch.tensor(q_valid, dtype=torch.long, device=dev), cache, linear=linear, plan_len=plan_len,
-                             fp8=fp8)
+                             **_quant_kw(quant))
         ids = target(logits, k, [len(out[b]) + t for b in range(n) for t in range(k)]).reshape(n, k).tolist()  # the host read
         adv = [0] * n
         for b in range(n):

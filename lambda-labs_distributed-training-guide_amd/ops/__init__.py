@@ -21,6 +21,7 @@ from .functional import (  # noqa: E402
     check_sample_scalar,
     decode_attention,
     decode_attention_multi,
+    dequantize_mxfp4,
     dropout_add_layer_norm,
     embedding,
     fused_linear_cross_entropy,
@@ -30,6 +31,7 @@ from .functional import (  # noqa: E402
     linear,
     qk_norm_rope,
     quantize_fp8_rows,
+    quantize_mxfp4_rows,
     rms_norm,
     rope,
     rope_tables,
@@ -37,6 +39,7 @@ from .functional import (  # noqa: E402
     skinny_linear,
     skinny_linear_fp8,
     skinny_linear_mfma,
+    skinny_linear_mxfp4,
     swiglu,
     swiglu_mlp,
     vocab_parallel_fused_linear_cross_entropy,
@@ -66,5 +69,5 @@ __all__ = [
     "rope_tables", "swiglu", "swiglu_mlp", "vocab_parallel_fused_linear_cross_entropy", "route_param_grad", "adamw_step",
     "fa_tuning", "layer_norm", "dropout_add_layer_norm", "gelu_mlp", "qk_norm_rope", "kv_cache_append", "decode_attention",
     "sample_logits", "skinny_linear", "skinny_linear_fp8", "quantize_fp8_rows", "decode_attention_multi",
-    "skinny_linear_mfma",
+    "skinny_linear_mfma", "skinny_linear_mxfp4", "quantize_mxfp4_rows", "dequantize_mxfp4",
 ]

@@ -235,9 +235,13 @@ SKINNY_MAX_M = 16  # rows of x the skinny kernels are instantiated for (kSkinnyM
 SKINNY_MFMA_MAX_M = 64  # rows of x the MFMA skinny kernel takes (kMfmaMaxM)
 
 
-def _skinny_check(name, x, w, act, chunk, w_layout, max_m=SKINNY_MAX_M):
+SKINNY_MXFP4_MAX_M = 64  # rows of x the MXFP4 skinny kernel takes (kMxMaxM)
+
+
+def _skinny_check(name, x, w, act, chunk, w_layout, max_m=SKINNY_MAX_M, pack=1):
     """The refusals the skinny operators share; `chunk` = the unit of K (weights per 16-B load, or the MFMA's
-    slab), `w_layout` the operator's own message for the weight matrix, `max_m` its row limit."""
+    slab), `w_layout` the operator's own message for the weight matrix, `max_m` its row limit, `pack` the
+    weights per element of `w` (2 for FP4 codes in bytes)."""
     if x.dtype != torch.bfloat16:
         raise RuntimeError(f"{name}: x must be a bf16 tensor")
     if act not in (0, 1):
@@ -248,7 +252,7 @@ def _skinny_check(name, x, w, act, chunk, w_layout, max_m=SKINNY_MAX_M):
         raise RuntimeError(f"{name}: K must be a multiple of {chunk}")
     if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
         raise RuntimeError(f"{name}: x must have unit inner stride and 16-B aligned rows")
-    if w.dim() != 2 or w.shape[1] != x.shape[1] or w.shape[0] < 1 or not w.is_contiguous() or w.data_ptr() % 16:
+    if w.dim() != 2 or w.shape[1] * pack != x.shape[1] or w.shape[0] < 1 or not w.is_contiguous() or w.data_ptr() % 16:
         raise RuntimeError(f"{name}: {w_layout}")
     if act and w.shape[0] % 2:
         raise RuntimeError(f"{name}: the SwiGLU epilogue needs an even N (gate rows, then up rows)")
@@ -296,6 +300,22 @@ def skinny_linear_fp8(x, wq, scale, bias, act=0):
     if scale.dtype != torch.float32 or scale.dim() != 1 or scale.shape[0] != wq.shape[0] or not scale.is_contiguous():
         raise RuntimeError(f"{name}: scale must be a contiguous f32 [N] on x's device")
     return _skinny_tail(name, (x.float() @ wq.float().t()) * scale, bias, act, x.dtype)
+
+
+def skinny_linear_mxfp4(x, wq, scales, bias, act=0):
+    """y = x @ deq(wq, scales)^T (+ bias) at 1 <= M <= 64 rows and K % 32 == 0: wq uint8 [N, K / 2] (two e2m1 codes
+    per byte), scales uint8 [N, K / 32] (e8m0); an f32 matmul on the dequantised matrix, one rounding; act = 1 as
+    skinny_linear (csrc/kernels/skinny_mxfp4.hip).  Refuses what the kernel refuses."""
+    from .functional import dequantize_mxfp4
+
+    name = "dtg: skinny_linear_mxfp4"
+    if wq.dtype != torch.uint8 or scales.dtype != torch.uint8:
+        raise RuntimeError(f"{name}: wq and scales must be uint8 tensors")
+    _skinny_check(name, x, wq, act, 32, "wq must be a contiguous 16-B aligned uint8 [N, K / 2] on x's device",
+                  SKINNY_MXFP4_MAX_M, pack=2)
+    if scales.dim() != 2 or scales.shape != (wq.shape[0], x.shape[1] // 32) or not scales.is_contiguous():
+        raise RuntimeError(f"{name}: scales must be a contiguous uint8 [N, K / 32] on x's device")
+    return _skinny_tail(name, x.float() @ dequantize_mxfp4(wq, scales).float().t(), bias, act, x.dtype)
 
 
 def swiglu_bwd(dh, gu):
@@ -928,6 +948,6 @@ for _name, _fn in list(globals().items()):
         "flash_attn_bwd_qkv_rope", "flash_attn_tuning", "layernorm_fwd", "dropout_add_layernorm_fwd", "layernorm_bwd",
         "gelu_fwd", "gelu_bwd", "gelu_bwd_t", "qk_norm_rope_fwd_", "qk_norm_rope_bwd_", "kv_cache_append_", "decode_attn",
         "sample_logits", "skinny_linear", "skinny_linear_fp8", "decode_attn_multi", "skinny_linear_mfma",
-        "kv_cache_append_fp8_", "decode_attn_fp8",
+        "kv_cache_append_fp8_", "decode_attn_fp8", "skinny_linear_mxfp4",
     ):
         LIB.impl(_name, _fn, "CPU")

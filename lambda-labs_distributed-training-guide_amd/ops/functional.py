@@ -12,7 +12,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from . import grad_routing as _gr
-from ._cpu import SKINNY_MAX_M, SKINNY_MFMA_MAX_M
+from ._cpu import SKINNY_MAX_M, SKINNY_MFMA_MAX_M, SKINNY_MXFP4_MAX_M
 from .grad_routing import route_embedding_grad, route_param_grad, route_weight_grad_mm
 
 ops = torch.ops.dtg
@@ -808,12 +808,12 @@ def swiglu(gu):
 _SKINNY_FUSED = os.environ.get("DTG_SKINNY_FUSED", "1") == "1"
 
 
-def _skinny_args(name, x, w, b, act, wname="w", max_m=SKINNY_MAX_M):
+def _skinny_args(name, x, w, b, act, wname="w", max_m=SKINNY_MAX_M, pack=1):
     """What the skinny operators (`name`, of at most `max_m` rows) share in argument handling; returns act as
-    0 / 1 and the bias as [N] or None."""
+    0 / 1 and the bias as [N] or None.  `pack`: weights per element of `w` (2 for FP4 codes in bytes)."""
     if act not in (None, 0, 1, "swiglu"):
         raise ValueError(f"{name}: act must be None or 'swiglu', got {act!r}")
-    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1] * pack:
         raise ValueError(f"{name}: x [M, K] and {wname} [N, K] do not match: {tuple(x.shape)}, {tuple(w.shape)}")
     if x.shape[0] > max_m:
         raise ValueError(f"{name}: M = {x.shape[0]} rows exceed the kernel's limit of {max_m}")
@@ -923,6 +923,80 @@ def skinny_linear_fp8(x, wq, scale, b=None, act=None):
             y = y + b.float()
         return _skinny_composed_tail(y.to(x.dtype), act)
     return ops.skinny_linear_fp8(x, wq, scale, b, act)
+
+
+# --------------------------------------------------------------------------------------------
+# Weight-only MXFP4 for the decode step (csrc/kernels/skinny_mxfp4.hip)
+# --------------------------------------------------------------------------------------------
+# OCP microscaling FP4 (MX v1.0): e2m1 elements (sign, two exponent bits, one mantissa bit) and one shared e8m0
+# power-of-two scale per block of 32 consecutive elements of a row: 4.25 bits per weight.
+MXFP4_BLOCK = 32
+MXFP4_MIN_EXP, MXFP4_MAX_EXP = -100, 125  # the block exponent k; the scale byte is k + 127, never 0 or 255
+MXFP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # magnitude of code & 7; bit 3 is the sign
+
+
+@torch.no_grad()
+def quantize_mxfp4_rows(w):
+    """Weight quantisation to MXFP4 (load time, torch ops): `w` bf16 / f32 [N, K], K % 32 == 0 ->
+    (wq uint8 [N, K / 2], scales uint8 [N, K / 32]).
+
+    Element 2 j of a row sits in the low nibble of byte j and element 2 j + 1 in the high nibble (the layout of
+    torch.float4_e2m1fn_x2).  scales[n, g] = k + 127 for block g of row n, k = floor(log2(amax_block)) - 2 clamped
+    to [-100, 125] (the OCP MX v1.0 rule; an all-zero block takes -100); the elements are v / 2^k rounded to the
+    nearest e2m1 value, ties to even, saturating at +-6.  The floor keeps every dequantised value a normal bf16
+    number."""
+    if w.dim() != 2 or w.dtype not in (torch.bfloat16, torch.float32) or w.shape[1] % MXFP4_BLOCK:
+        raise ValueError(f"quantize_mxfp4_rows: w must be a bf16 or f32 [N, K] matrix with K % {MXFP4_BLOCK} == 0, got "
+                         f"{w.dtype} {tuple(w.shape)}")
+    N, K = w.shape
+    v = w.detach().float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = v.abs().amax(dim=2) if K else v.new_zeros(N, 0)
+    if not bool(torch.isfinite(amax).all()):
+        raise ValueError("quantize_mxfp4_rows: w holds non-finite values")
+    # amax = m * 2^e with m in [0.5, 1) (frexp is exact): floor(log2(amax)) = e - 1
+    k = (torch.frexp(amax)[1].to(torch.int32) - 3).clamp(MXFP4_MIN_EXP, MXFP4_MAX_EXP)
+    k = torch.where(amax == 0, torch.full_like(k, MXFP4_MIN_EXP), k)
+    q = v / _pow2(k)[..., None]  # exact: a division by a power of two
+    a = q.abs().clamp_(max=6.0)
+    # the e2m1 grid has spacing 0.5 below 2, 1 below 4 and 2 up to 6; torch.round rounds halves to even, and an
+    # even count of steps is an even mantissa bit in each of the three ranges
+    code = torch.where(a < 2.0, torch.round(a * 2.0), torch.where(a < 4.0, torch.round(a) + 2.0, torch.round(a * 0.5) + 4.0))
+    code = (code.to(torch.uint8) | (torch.signbit(q).to(torch.uint8) << 3)).reshape(N, K // 2, 2)  # the sign is kept: -0 too
+    wq = (code[..., 0] | (code[..., 1] << 4)).contiguous()
+    return wq, (k + 127).to(torch.uint8).contiguous()
+
+
+@torch.no_grad()
+def dequantize_mxfp4(wq, scales):
+    """The bf16 [N, K] matrix that (wq, scales) of `quantize_mxfp4_rows` stand for.  Exact: a 2-bit significand
+    times a power of two is a bf16 value."""
+    if (wq.dim() != 2 or scales.dim() != 2 or wq.dtype != torch.uint8 or scales.dtype != torch.uint8
+            or wq.shape[0] != scales.shape[0] or wq.shape[1] * 2 != scales.shape[1] * MXFP4_BLOCK):
+        raise ValueError(f"dequantize_mxfp4: need wq uint8 [N, K / 2] and scales uint8 [N, K / 32], got {wq.dtype} "
+                         f"{tuple(wq.shape)} and {scales.dtype} {tuple(scales.shape)}")
+    N, K = wq.shape[0], wq.shape[1] * 2
+    lut = torch.tensor(MXFP4_VALUES + tuple(-m for m in MXFP4_VALUES), dtype=torch.float32, device=wq.device)
+    codes = torch.stack([wq & 15, wq >> 4], dim=2).reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    scale = (scales.to(torch.int32) << 23).view(torch.float32)
+    return (lut[codes.long()] * scale[..., None]).reshape(N, K).to(torch.bfloat16)
+
+
+@torch.no_grad()
+def skinny_linear_mxfp4(x, wq, scales, b=None, act=None):
+    """y = x @ dequantize_mxfp4(wq, scales)^T (+ b) for 1 <= M <= 64 bf16 rows of x [M, K], K % 32 == 0:
+    `ops.skinny_linear_mfma` with the weights streamed as MXFP4, 4.25 bits each, and widened in registers by
+    v_cvt_scalef32_pk_bf16_fp4 (csrc/kernels/skinny_mxfp4.hip).  `wq` / `scales` as `quantize_mxfp4_rows` returns
+    them.  The same `act` (bitwise `swiglu(skinny_linear_mxfp4(x, wq, scales, b))`) and the same promise: f32
+    accumulation in an order that depends on K alone, so a row's result is the same alone and inside any batch of
+    up to 64 rows."""
+    act, b = _skinny_args("skinny_linear_mxfp4", x, wq, b, act, wname="wq", max_m=SKINNY_MXFP4_MAX_M, pack=2)
+    if scales.dim() != 2 or scales.shape != (wq.shape[0], x.shape[1] // MXFP4_BLOCK):
+        raise ValueError(f"skinny_linear_mxfp4: scales must be [N = {wq.shape[0]}, K / 32 = {x.shape[1] // MXFP4_BLOCK}], "
+                         f"got {tuple(scales.shape)}")
+    if x.is_cuda and not (_SKINNY_FUSED and x.dtype == torch.bfloat16):
+        w = dequantize_mxfp4(wq, scales).to(x.dtype)
+        return _skinny_composed_tail(torch.mm(x, w.t()) if b is None else torch.addmm(b, x, w.t()), act)
+    return ops.skinny_linear_mxfp4(x, wq, scales, b, act)
 
 
 def _mlp_backward(act, x, w1, w2, a, dy, b1=None, b2=None):

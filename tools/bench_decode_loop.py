@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""The decode loop of dtg.generate in its eight forms -- projections in hipBLASLt, in the skinny-GEMM kernel,
-in the weight-only FP8 skinny-GEMM kernel or in the MFMA skinny-GEMM kernel, the loop eager or captured into
+"""The decode loop of dtg.generate in its ten forms -- projections in hipBLASLt, in the skinny-GEMM kernel,
+in the weight-only FP8 skinny-GEMM kernel, in the MFMA skinny-GEMM kernel or in the weight-only MXFP4 MFMA
+skinny-GEMM kernel, the loop eager or captured into
 HIP graphs -- on random-init Qwen3-0.6B and Llama-3.2-1B, batch 1 and 8 (--batches; an arm is left out where
-the batch exceeds its mode's row limit), a 16-token prompt and 256 new tokens, greedy.  The FP8 copies are
+the batch exceeds its mode's row limit), a 16-token prompt and 256 new tokens, greedy.  The FP8 and MXFP4 copies are
 quantised once per model, outside every clock; a step reads every matrix once, and both models' matrices
 (0.6-2.5 GB in either format) exceed the 256 MB Infinity Cache, so no arm re-reads its weights from a cache.
 
@@ -29,19 +30,21 @@ MODELS = ("qwen3-0.6b", "llama-3.2-1b")
 BATCHES = (1, 8)
 PROMPT, NEW, WARM = 16, 256, 8
 ARMS = [("blas", "eager"), ("skinny", "eager"), ("skinny-fp8", "eager"), ("blas", "graph"), ("skinny", "graph"),
-        ("skinny-fp8", "graph"), ("skinny-mfma", "eager"), ("skinny-mfma", "graph")]
+        ("skinny-fp8", "graph"), ("skinny-mfma", "eager"), ("skinny-mfma", "graph"), ("skinny-mxfp4", "eager"),
+        ("skinny-mxfp4", "graph")]
 
 
-def run_arm(torch, model, prompts, linear, decode, s_max, fp8=None):
+def run_arm(torch, model, prompts, linear, decode, s_max, quant=None):
     """One generate()-equivalent run; returns (tokens / s of the timed steps, capture seconds, first row's ids)."""
     from dtg.models.decode_graph import GraphedDecode
     from dtg.models.generation import KVCache, decode_bucket, decode_step, prefill
 
     n = len(prompts)
-    fp8 = fp8 if linear == "skinny-fp8" else None  # quantised once per model, outside every clock
+    # quantised once per model, outside every clock: {"fp8": ...} / {"mxfp4": ...} for the two quantised modes
+    quant = {k: v for k, v in (quant or {}).items() if v.mode == linear}
     if decode == "graph":
         # the loop of GraphedDecode.run with a clock in it: two runs on one object, the first captures
-        gd = GraphedDecode(model, n, s_max, linear=linear, fp8=fp8)
+        gd = GraphedDecode(model, n, s_max, linear=linear, **quant)
         gd.run(prompts, WARM + 4)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -51,20 +54,20 @@ def run_arm(torch, model, prompts, linear, decode, s_max, fp8=None):
         # the second run replays from its first step; its prefill is measured on its own and subtracted
         t1 = time.perf_counter()
         gd.reset()
-        prefill(model, prompts, gd.cache, fp8=fp8)
+        prefill(model, prompts, gd.cache, **quant)
         torch.cuda.synchronize()
         pre = time.perf_counter() - t1
         return n * (NEW - 1) / max(dt - pre, 1e-9), gd.capture_seconds, out[0]
     dev = model.embed_tokens.weight.device
     cache = KVCache(model.config, n, s_max, device=dev, dtype=model.embed_tokens.weight.dtype)
-    nxt = prefill(model, prompts, cache, fp8=fp8).argmax(-1)
+    nxt = prefill(model, prompts, cache, **quant).argmax(-1)
     ids = [nxt]
     for step in range(1, NEW):
         if step == WARM:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
         nxt = decode_step(model, nxt, cache, linear=linear, plan_len=decode_bucket(cache.max_len + 1, s_max),
-                          fp8=fp8).argmax(-1)
+                          **quant).argmax(-1)
         ids.append(nxt)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -83,7 +86,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_decode_loop: needs a GPU")
     import dtg  # noqa: F401
-    from dtg.models import Fp8DecodeWeights, build_model, resolve_config
+    from dtg.models import Fp8DecodeWeights, Mxfp4DecodeWeights, build_model, resolve_config
     from dtg.models.generation import linear_max_rows
 
     dev = torch.device("cuda:0")
@@ -92,7 +95,7 @@ def main():
         cfg = resolve_config(name)
         torch.manual_seed(0)
         model = build_model(cfg, device=dev).eval()
-        fp8 = Fp8DecodeWeights(model)
+        quant = {"fp8": Fp8DecodeWeights(model), "mxfp4": Mxfp4DecodeWeights(model)}
         for n in map(int, a.batches.split(",")):
             arms = [arm for arm in ARMS if n <= (linear_max_rows(arm[0]) or n)]
             g = torch.Generator().manual_seed(n)
@@ -104,7 +107,7 @@ def main():
             with torch.no_grad():
                 for _ in range(a.rounds):
                     for arm in arms:
-                        tps, c, first = run_arm(torch, model, prompts, arm[0], arm[1], s_max, fp8)
+                        tps, c, first = run_arm(torch, model, prompts, arm[0], arm[1], s_max, quant)
                         res[arm].append(tps)
                         cap[arm] = max(cap[arm], c)
                         ids[arm] = first
@@ -118,7 +121,7 @@ def main():
                      "ids_equal_eager_same_linear": bool(torch.equal(ids[arm], ids[(arm[0], "eager")]))}
                 print(json.dumps(r), flush=True)
                 rows.append(r)
-        del model, fp8
+        del model, quant
         torch.cuda.empty_cache()
     if a.md:
         with open(a.md, "w") as fp:

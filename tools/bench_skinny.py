@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
 """ops.skinny_linear (csrc/kernels/skinny_gemm.hip), ops.skinny_linear_fp8 (the same kernel, weight-only
-e4m3) and ops.skinny_linear_mfma (csrc/kernels/skinny_mfma.hip) against hipBLASLt (torch.mm / addmm, +
+e4m3), ops.skinny_linear_mfma (csrc/kernels/skinny_mfma.hip) and ops.skinny_linear_mxfp4 (weight-only MXFP4,
+csrc/kernels/skinny_mxfp4.hip) against hipBLASLt (torch.mm / addmm, +
 ops.swiglu for the gate_up projection) in the same process, at the decode-step projection shapes of Llama-3-8B
 (and the two narrow ones of Llama-3.2-1B and Qwen3-0.6B) and M = 1, 4, 8, 16, 32, 64 rows: time per call from
 HIP events and the rate at which the weight bytes are consumed (the FP8 arm's GB/s counts its one-byte
-weights).  The fmaf arms (bf16 and fp8) stop at their 16-row limit.
+weights, the MXFP4 arm's its 17 bytes per 32 weights).  The fmaf arms (bf16 and fp8) stop at their 16-row limit.
 
 Every call of a timing takes the next of `copies` distinct weight buffers, enough that the set exceeds
 the 256 MB Infinity Cache (--min-set-mb), so a weight is never re-read from a cache and the figure is an
-HBM rate (profiles/r7/decode/README.md explains the trap); the FP8 arm has its own, more numerous, buffers
-for the same total.  The paths alternate; each keeps the better median.  Needs a GPU.
+HBM rate (profiles/r7/decode/README.md explains the trap); the FP8 and MXFP4 arms have their own, more numerous,
+buffers for the same total.  The paths alternate; each keeps the better of its two medians, and the gap between
+the two (relative to the better) is reported as the arm's spread for the MXFP4 and FP8 arms: call one faster only
+when the gap between them exceeds both spreads.  Needs a GPU.
 
     python tools/bench_skinny.py [--md OUT.md]
 """
@@ -73,6 +76,9 @@ def main():
         ws = [(torch.randn(N, K, device=dev) / K ** 0.5).to(torch.bfloat16) for _ in range(copies)]
         copies8 = max(2, int(a.min_set_mb * 1e6 / (N * K)) + 1)
         w8 = [ops.quantize_fp8_rows(ws[j % copies]) for j in range(copies8)]  # distinct buffers, values repeat
+        mxbytes = N * K * 17 // 32  # codes and block scales
+        copies4 = max(2, int(a.min_set_mb * 1e6 / mxbytes) + 1)
+        w4 = [ops.quantize_mxfp4_rows(ws[j % copies]) for j in range(copies4)]
         for M in map(int, a.ms.split(",")):
             x = torch.randn(M, K, device=dev).to(torch.bfloat16)
             i = [0]
@@ -89,36 +95,46 @@ def main():
                 i[0] = (i[0] + 1) % copies8
                 return ops.skinny_linear_fp8(x, w8[i[0]][0], w8[i[0]][1], None, act="swiglu" if act else None)
 
+            def mx4():
+                i[0] = (i[0] + 1) % copies4
+                return ops.skinny_linear_mxfp4(x, w4[i[0]][0], w4[i[0]][1], None, act="swiglu" if act else None)
+
             def blas():
                 i[0] = (i[0] + 1) % copies
                 y = torch.mm(x, ws[i[0]].t())
                 return ops.swiglu(y) if act else y
 
-            res = {}
-            arms = (("mfma", mfma), ("blas", blas)) + ((("kernel", kernel), ("fp8", fp8)) if M <= FMAF_MAX_M else ())
+            res, spread = {}, {}
+            arms = (("mfma", mfma), ("mx4", mx4), ("blas", blas)) + ((("kernel", kernel), ("fp8", fp8)) if M <= FMAF_MAX_M else ())
             for which, fn in arms * 2:
                 t = time_ms(torch, fn, a.min_ms)
+                spread[which] = round(100 * abs(res.get(which, t) - t) / min(res.get(which, t), t), 1)
                 res[which] = min(res.get(which, t), t)
             r = {"proj": name, "N": N, "K": K, "M": M, "copies": copies, "mfma_us": round(res["mfma"] * 1e3, 1),
                  "mfma_GBps": round(wbytes / res["mfma"] / 1e6, 1), "blas_over_mfma": round(res["blas"] / res["mfma"], 2),
-                 "blas_us": round(res["blas"] * 1e3, 1), "blas_GBps": round(wbytes / res["blas"] / 1e6, 1)}
+                 "blas_us": round(res["blas"] * 1e3, 1), "blas_GBps": round(wbytes / res["blas"] / 1e6, 1),
+                 "mx4_copies": copies4, "mx4_us": round(res["mx4"] * 1e3, 1), "mx4_spread_pct": spread["mx4"],
+                 "mx4_GBps": round(mxbytes / res["mx4"] / 1e6, 1), "mfma_over_mx4": round(res["mfma"] / res["mx4"], 2)}
             if M <= FMAF_MAX_M:
                 r.update({"kernel_us": round(res["kernel"] * 1e3, 1), "kernel_GBps": round(wbytes / res["kernel"] / 1e6, 1),
                           "blas_over_kernel": round(res["blas"] / res["kernel"], 2),
                           "kernel_over_mfma": round(res["kernel"] / res["mfma"], 2),
                           "fp8_copies": copies8, "fp8_us": round(res["fp8"] * 1e3, 1),
                           "fp8_GBps": round(N * K / res["fp8"] / 1e6, 1),
-                          "kernel_over_fp8": round(res["kernel"] / res["fp8"], 2)})
+                          "kernel_over_fp8": round(res["kernel"] / res["fp8"], 2), "fp8_spread_pct": spread["fp8"],
+                          "fp8_over_mx4": round(res["fp8"] / res["mx4"], 2)})
             print(json.dumps(r), flush=True)
             out.append(r)
-        del ws, w8
+        del ws, w8, w4
         torch.cuda.empty_cache()
     if a.md:
         with open(a.md, "w") as fp:
-            cols = ["mfma_us", "kernel_us", "fp8_us", "blas_us", "mfma_GBps", "kernel_GBps", "fp8_GBps", "blas_GBps",
-                    "blas_over_mfma", "kernel_over_mfma", "blas_over_kernel", "kernel_over_fp8"]
-            fp.write("| projection | N x K | M | mfma kernel µs | fmaf kernel µs | fp8 kernel µs | hipBLASLt µs | "
-                     "mfma GB/s (weights) | fmaf GB/s (weights) | fp8 GB/s (fp8 bytes) | hipBLASLt GB/s | hipBLASLt / mfma | "
+            cols = ["mx4_us", "mfma_us", "kernel_us", "fp8_us", "blas_us", "mx4_GBps", "mfma_GBps", "kernel_GBps", "fp8_GBps",
+                    "blas_GBps", "mx4_spread_pct", "fp8_spread_pct", "fp8_over_mx4", "mfma_over_mx4", "blas_over_mfma",
+                    "kernel_over_mfma", "blas_over_kernel", "kernel_over_fp8"]
+            fp.write("| projection | N x K | M | mxfp4 kernel µs | mfma kernel µs | fmaf kernel µs | fp8 kernel µs | hipBLASLt µs | "
+                     "mxfp4 GB/s (mxfp4 bytes) | mfma GB/s (weights) | fmaf GB/s (weights) | fp8 GB/s (fp8 bytes) | "
+                     "hipBLASLt GB/s | mxfp4 spread % | fp8 spread % | fp8 / mxfp4 | mfma / mxfp4 | hipBLASLt / mfma | "
                      "fmaf / mfma | hipBLASLt / fmaf | fmaf / fp8 |\n")
             fp.write("|---" * (3 + len(cols)) + "|\n")
             for r in out:

@@ -3,7 +3,7 @@
 kernel (ops.decode_attention_multi) against Q launches of ops.decode_attention, in one process.
 
 Loop: tokens / s of `generate` at batch 1 and 4 (--batches) on Qwen3-0.6B and a Llama-3.2-1B-shaped model (random
-init), linear = blas / skinny / skinny-fp8 / skinny-mfma (a mode is left out where batch x k exceeds its row
+init), linear = blas / skinny / skinny-fp8 / skinny-mfma / skinny-mxfp4 (a mode is left out where batch x k exceeds its row
 limit), greedy, for the plain loop and for the speculative loop under three drafters:
   oracle  proposes the plain run's own ids: everything is accepted, the ceiling of the mode;
   wrong   proposes ids that are never right: one id per verify pass, the floor (the cost of a wasted verify);
@@ -63,7 +63,7 @@ def main():
         raise SystemExit("bench_speculative: needs a GPU")
     import dtg  # noqa: F401
     from dtg import ops
-    from dtg.models import Fp8DecodeWeights, Speculative, build_model, generate, resolve_config
+    from dtg.models import Fp8DecodeWeights, Mxfp4DecodeWeights, Speculative, build_model, generate, resolve_config
     from dtg.models.generation import linear_max_rows
 
     dev = torch.device("cuda:0")
@@ -88,17 +88,18 @@ def main():
         cfg = resolve_config(base_name, **over)
         torch.manual_seed(0)
         model = build_model(cfg, device=dev).eval()
-        fp8_w = Fp8DecodeWeights(model)
+        fp8_w, mx_w = Fp8DecodeWeights(model), Mxfp4DecodeWeights(model)
         for batch in map(int, a.batches.split(",")):
             g = torch.Generator().manual_seed(batch)
             piece = torch.randint(0, cfg.vocab_size, (a.prompt_len // 4,), generator=g)
             prompts = {"random": [torch.randint(0, cfg.vocab_size, (a.prompt_len,), generator=g) for _ in range(batch)],
                        "repeat": [piece.roll(i).repeat(4) for i in range(batch)]}
             s_max = a.prompt_len + a.new
-            for linear in ("blas", "skinny", "skinny-fp8", "skinny-mfma"):
+            for linear in ("blas", "skinny", "skinny-fp8", "skinny-mfma", "skinny-mxfp4"):
                 if batch * a.k > (linear_max_rows(linear) or batch * a.k):
                     continue
-                kw = dict(s_max=s_max, linear=linear, fp8=fp8_w if linear == "skinny-fp8" else None)
+                kw = dict(s_max=s_max, linear=linear, fp8=fp8_w if linear == "skinny-fp8" else None,
+                          mxfp4=mx_w if linear == "skinny-mxfp4" else None)
                 plain = {}
                 for which, pr in prompts.items():
                     t, ids = timed(lambda pr=pr: generate(model, pr, a.new, **kw))
@@ -120,7 +121,7 @@ def main():
                          "accepted": st["accepted"], "ids_equal": all(torch.equal(x, y) for x, y in zip(ids, ref))}
                     print(json.dumps(r), flush=True)
                     loop_rows.append(r)
-        del model, fp8_w
+        del model, fp8_w, mx_w
         torch.cuda.empty_cache()
 
     NQ, NKV, D = 32, 8, 128
