@@ -81,11 +81,11 @@ def build(jobs: int | None = None, force: bool = False, verbose: bool = False, o
     # allocator placed the S / dP tiles in the same AGPRs and copied 32-64 accumulator registers
     # out and back (v_accvgpr_read/write) every item -- 96-128 extra VALU per 32-96 MFMAs in
     # the loop (ISA counted with llvm-objdump).  The VGPR form removes all of them, no spills.
-    # host_mem.hip, skinny_mfma.hip, skinny_mxfp4.hip: built without packed-f32 VALU ops (v_pk_*_f32), as all new
+    # host_mem.hip, skinny_mfma.hip: built without packed-f32 VALU ops (v_pk_*_f32), as all new
     # HIP code is.
     no_pk = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     per_file = {"flash_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-                "host_mem.hip": no_pk, "skinny_mfma.hip": no_pk, "skinny_mxfp4.hip": no_pk} if per_file_flags else {}
+                "host_mem.hip": no_pk, "skinny_mfma.hip": no_pk} if per_file_flags else {}
     srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")) + glob.glob(os.path.join(CSRC, "comm", "*.hip")))
     cpu_srcs = sorted(glob.glob(os.path.join(CSRC, "cpu", "*.cpp")))
     hdr_t = _newest_header()

@@ -34,6 +34,7 @@
 // number of bytes: this form reads half of them.  bf16 x e4m3 products are exact in f32 (8 + 4 significand
 // bits).  More than 8 rows of x run one pass deep.
 #include "mlp_act.h"
+#include "skinny_common.h"
 
 namespace dtg {
 
@@ -179,49 +180,17 @@ __global__ __launch_bounds__(kSkinnyThreads) void skinny_gemm_kernel(
   }
 }
 
-// What the operators share on the host: the checks on x, act, M, K, the weight matrix's layout (`w_layout` is
-// the operator's own message for it) and the bias, and the grid.  The operators check the weights' dtype
-// before and the scale after.
-struct SkinnyPlan {
-  int64_t M, N, K;
-  const uint16_t* bias = nullptr;
-  unsigned grid;
-};
-
+// The shared checks with this kernel's limits: up to 16 rows, K in whole 16-B loads, one weight per element.
 template <class Fmt>
-SkinnyPlan skinny_plan(const char* name, const char* w_layout, const at::Tensor& x, const at::Tensor& w,
-                       const c10::optional<at::Tensor>& bias, int64_t act) {
-  SkinnyPlan p;
-  DTG_CHECK_CUDA_BF16(x);
-  DTG_CHECK(act == 0 || act == 1, name, ": act must be 0 (none) or 1 (SwiGLU)");
-  DTG_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(0) <= kSkinnyMaxM, name, ": x must be [M, K] with 1 <= M <= ",
-            kSkinnyMaxM);
-  p.M = x.size(0), p.K = x.size(1);
-  DTG_CHECK(p.K % Fmt::kChunk == 0, name, ": K must be a multiple of ", Fmt::kChunk);
-  DTG_CHECK(x.stride(1) == 1 && x.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, name,
-            ": x must have unit inner stride and 16-B aligned rows");
-  DTG_CHECK(w.dim() == 2 && w.size(1) == p.K && w.size(0) >= 1 && w.is_contiguous() && w.device() == x.device() &&
-                reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
-            name, w_layout);
-  p.N = w.size(0);
-  DTG_CHECK(act == 0 || p.N % 2 == 0, name, ": the SwiGLU epilogue needs an even N (gate rows, then up rows)");
-  DTG_CHECK(p.N < (int64_t(1) << 32) && p.K < (int64_t(1) << 40), name, ": matrix too large");
-  if (bias.has_value() && bias->defined()) {
-    DTG_CHECK_CUDA_BF16(*bias);
-    DTG_CHECK(bias->dim() == 1 && bias->size(0) == p.N && bias->is_contiguous() && bias->device() == x.device(), name,
-              ": bias must be a contiguous [N]");
-    p.bias = bf16_ptr(*bias);
-  }
-  const int64_t cols_per_wg = (int64_t)kSkinnyWaves * (act ? kRows / 2 : kRows);
-  const int64_t nwg = ((act ? p.N / 2 : p.N) + cols_per_wg - 1) / cols_per_wg;
-  DTG_CHECK(nwg < (int64_t(1) << 31), name, ": too many workgroups");
-  p.grid = (unsigned)nwg;
-  return p;
+skinny::Plan skinny_plan(const char* name, const char* w_layout, const at::Tensor& x, const at::Tensor& w,
+                         const c10::optional<at::Tensor>& bias, int64_t act) {
+  return skinny::plan(name, w_layout, kSkinnyMaxM, Fmt::kChunk, 1, kSkinnyWaves * (act ? kRows / 2 : kRows), x, w,
+                      bias, act);
 }
 
 // Launches the instantiation for p.M rows of x: M counts down from the largest.
 template <class Fmt, int ACT, int M = kSkinnyMaxM>
-void skinny_launch(const SkinnyPlan& p, const at::Tensor& x, const at::Tensor& w, typename Fmt::Scale scale,
+void skinny_launch(const skinny::Plan& p, const at::Tensor& x, const at::Tensor& w, typename Fmt::Scale scale,
                    at::Tensor& y) {
   if constexpr (M >= 1) {
     if (p.M != M) return skinny_launch<Fmt, ACT, M - 1>(p, x, w, scale, y);
@@ -232,7 +201,7 @@ void skinny_launch(const SkinnyPlan& p, const at::Tensor& x, const at::Tensor& w
 }
 
 template <class Fmt>
-at::Tensor skinny_run(const SkinnyPlan& p, const at::Tensor& x, const at::Tensor& w, typename Fmt::Scale scale,
+at::Tensor skinny_run(const skinny::Plan& p, const at::Tensor& x, const at::Tensor& w, typename Fmt::Scale scale,
                       int64_t act) {
   const c10::DeviceGuard g(x.device());
   auto y = at::empty({p.M, act ? p.N / 2 : p.N}, x.options());

@@ -1,84 +1,170 @@
-// MFMA skinny GEMM for decode and verify steps of up to 64 rows: y[M, N] = x[M, K] @ w[N, K]^T (+ bias),
-// 1 <= M <= 64, K % 32 == 0, all bf16, f32 accumulation, one rounding.  At these M the product is still a
-// weight-streaming problem (64 flop per weight byte at M = 64), but the fmaf kernel of skinny_gemm.hip runs out
+// MFMA skinny GEMMs for decode and verify steps of up to 64 rows: y[M, N] = x[M, K] @ W[N, K]^T (+ bias),
+// 1 <= M <= 64, K % 32 == 0, x, bias and y bf16, f32 accumulation, one rounding.  At these M the product is still
+// a weight-streaming problem (64 flop per weight byte at M = 64), but the fmaf kernel of skinny_gemm.hip runs out
 // of VALU and registers long before its 16-row limit.  Here the weights go to v_mfma_f32_16x16x32_bf16: the
 // single read of every weight stays, and a row of x costs a quarter of an MFMA per 512 weights instead of
-// 512 fmaf.
+// 512 fmaf.  One kernel template serves every weight format; a format (below) says how the weights of one step
+// of the K loop reach the A fragments of its MFMAs and nothing else.
 //
-// Operands.  Both matrices are K-contiguous and so is a lane's 8-element slice of a 16x16x32 operand, so
-// both go from global memory straight into operand registers with one 16-B load per lane; nothing is staged
-// in LDS.  For the 32-wide K slab at k0, lane l loads
-//   A (weights): 8 elements of weight row n0 + (l & 15) at k0 + 8 * (l >> 4), non-temporal (read once);
-//   B (x):       8 elements of x row m0 + (l & 15) at the same k, default policy (every workgroup re-reads x,
-//                it lives in L1 / L2).
-// A and B share the k mapping, so the k order inside a slab is the hardware's own business.  The accumulator
-// of lane l is C[4 * (l >> 4) + r][l & 15], r = 0..3: output columns n0 + 4 * (l >> 4) + r of x row
+// Operands.  Both matrices are K-contiguous and so is a lane's 8-element slice of a 16x16x32 operand, so both go
+// from global memory straight into registers with 16-B loads; nothing is staged in LDS.  The K loop steps in
+// units of kUnit elements, kMfmas = kUnit / 32 MFMAs each, and lane group kq = l >> 4 owns a quarter of a unit:
+// elements kq * kUnit / 4 + 8 i + j, j = 0..7, are its slice of MFMA i.  For unit s, lane l loads
+//   A (weights): its quarter of weight row n0 + (l & 15), as the format says, non-temporal (read once);
+//   B (x):       for MFMA i, 8 elements of x row m0 + (l & 15) at s * kUnit + kq * kUnit / 4 + 8 i, default
+//                policy (every workgroup re-reads x, it lives in L1 / L2).
+// A and B share the k mapping, so which k the hardware calls which inside an MFMA does not matter.  The
+// accumulator of lane l is C[4 * (l >> 4) + r][l & 15], r = 0..3: output columns n0 + 4 * (l >> 4) + r of x row
 // m0 + (l & 15).  Weight rows past N are clamped to row N - 1 and x rows past M to row M - 1: loaded, never
 // stored.
 //
 // Work split.  A workgroup owns one 16-column tile of the output (with the SwiGLU epilogue the gate tile and
-// the matching up tile) and all rows of x.  Its kWaves = 8 waves split K: wave v takes slabs v, v + 8, ...
-// MT = ceil(M / 16) is a template parameter; per slab a wave issues one weight load (two with act), MT x
-// loads and MT (2 MT) MFMAs into MT f32x4 accumulators.  The slab loop runs kUnroll = 8 slabs per pass: the 8
-// weight loads of a pass (8 KB per wave, 16 KB with act) are issued before its first MFMA.  A last partial
-// pass runs the same body with wave-uniform guards.
+// the matching up tile) and all rows of x.  Its kWaves = 8 waves split K: wave v takes units v, v + 8, ...
+// MT = ceil(M / 16) is a template parameter; per unit a wave issues one weight load (two with act), kMfmas * MT
+// x loads and kMfmas * MT (2 MT with act) MFMAs into MT f32x4 accumulators per weight tile.  The loop runs
+// kUnroll units per pass: every weight load of a pass is issued before its first conversion or MFMA.  A last
+// partial pass runs the same body with guards: a unit that does not exist is skipped (wave-uniform), and in a
+// last unit that K cuts short the lanes whose quarter lies past K load nothing and put zeros into both
+// fragments, so they add exact zeros.
 //
 // Reduction.  Every wave writes its partial accumulators to LDS; after one barrier wave t < MT adds the
 // partials of M tile t in ascending wave order, adds the bias, rounds and stores its own outputs.  No atomics,
 // no split-K across workgroups.
 //
-// Summation order of output (m, n): inside a slab the hardware's, slabs ascending within a wave, waves
-// ascending.  It depends on K alone: M, MT, the other rows and the slot of the tile do not enter it, so row m
-// of a batched call equals the single-row call bit for bit.
+// Summation order of output (m, n): inside an MFMA the hardware's, the MFMAs of a unit ascending, units
+// ascending within a wave, waves ascending.  It depends on K and the format alone: M, MT, the other rows and the
+// slot of the tile do not enter it, so row m of a batched call equals the single-row call bit for bit.
 //
-// Epilogue as skinny_gemm.hip: act = 1 (SwiGLU) biases and rounds the gate and the up sum each as the plain
-// form stores them, widens them and passes them through mlp_act::SwiGLU::fwd: bitwise swiglu_fwd of the plain
-// product.
+// Epilogue as skinny_gemm.hip (skinny::store): act = 1 (SwiGLU) biases and rounds the gate and the up sum each
+// as the plain form stores them, widens them and passes them through mlp_act::SwiGLU::fwd: bitwise swiglu_fwd of
+// the plain product.
 //
-// Known costs.  A workgroup re-reads all of x: the L1 / L2 traffic for x is M / 16 times the weight traffic
-// (4x at M = 64).  The grid is ceil(N / 16) workgroups, so N = 1024 fills a quarter of the CUs.  A K of fewer
-// than 32 * 8 * 8 elements never runs a full pass.  See profiles/r8/skinny_mfma/README.md.
+// Known costs of every format.  A workgroup re-reads all of x: the L1 / L2 traffic for x is M / 16 times the
+// traffic of as many bf16 weights (4x at M = 64).  The grid is ceil(N / 16) workgroups, so N = 1024 fills a
+// quarter of the CUs.
+//
+// Bf16Mfma (skinny_linear_mfma): a unit is one MFMA, and a lane's 16-B load is its A fragment as it stands.
+// K % 32 == 0 is the unit, so no unit is cut short.  kUnroll = 8: the 8 weight loads of a pass are 8 KB per
+// wave, 16 KB with act.  A K of fewer than 32 * 8 * 8 elements never runs a full pass.  See
+// profiles/r8/skinny_mfma/README.md.
+//
+// Mxfp4Mfma (skinny_linear_mxfp4): weight-only OCP microscaling FP4, y = x @ deq(wq, scales)^T.  e2m1 codes,
+// two per byte (element 2 j in the low nibble of byte j), and one e8m0 byte per block of 32 consecutive
+// elements of a row, 4.25 bits per weight streamed.  gfx950 widens the format in hardware:
+// v_cvt_scalef32_pk_bf16_fp4 turns the two codes of one byte into two bf16 values and multiplies them by the
+// block's scale in the same instruction.  A code times a power of two is exactly a bf16 value, so the kernel
+// computes the bf16 product of Bf16Mfma on the dequantised matrix, with the same promises.  One 16-B load holds
+// 32 codes: exactly one MX block, so a unit is 128 elements (four MFMAs) and a lane's quarter is the block kq of
+// its row: one 16-B load at byte (128 s + 32 kq) / 2 of the row and one byte load of the block's scale, which
+// becomes a float by uint32(byte) << 23.  Dword i of the load widens, through four conversions with byte selects
+// 0..3, into the A fragment of the unit's i-th MFMA.  K % 128 != 0 cuts the last unit short: lane group kq has
+// a block only when 4 s + kq < K / 32.  The format guarantees the kernel relies on (ops.quantize_mxfp4_rows):
+// scale bytes 0 and 255 never occur, so byte << 23 is a normal power of two and never NaN.  A 16-B load covers
+// four times the K of the bf16 form's, so K = 4096 is only 32 units, four per wave, and the bf16 form's eight
+// per pass do not carry over: kUnroll = 2 was measured fastest against 4 and 8
+// (profiles/r8/skinny_mxfp4/README.md; -DDTG_MXFP4_UNROLL=n builds the others).  Its own costs: 16 conversions
+// per four MFMAs and per weight tile run on the VALU in front of the matrix pipe; at 4.25 bits per weight the
+// traffic for x is 3.8 M / 16 times the weight traffic, 15x at M = 64; a scale byte is a 1-B load per lane per
+// unit.
 #include "mlp_act.h"
+#include "skinny_common.h"
 
 namespace dtg {
 
 namespace {
 
 constexpr int kMfmaMaxM = 64;
-constexpr int kWaves = 8;   // waves of a workgroup; they split K
-constexpr int kUnroll = 8;  // slabs per pass: weight loads in flight per wave
-constexpr int kSlab = 32;   // K elements of one MFMA
-constexpr int kTile = 16;   // output columns of a workgroup, rows of x per MFMA
+constexpr int kWaves = 8;  // waves of a workgroup; they split K
+constexpr int kTile = 16;  // output columns of a workgroup, rows of x per MFMA
+#ifndef DTG_MXFP4_UNROLL
+#define DTG_MXFP4_UNROLL 2
+#endif
 
-__device__ __forceinline__ bf16x8 frag(const uint16_t* p) {
-  return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u16x8*>(p));
-}
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ bf16x8 frag_nt(const uint16_t* p) {
-  return __builtin_bit_cast(bf16x8, __builtin_nontemporal_load(reinterpret_cast<const u16x8*>(p)));
-}
+struct Bf16Mfma {
+  static constexpr int kUnit = 32;     // K elements of one loop step
+  static constexpr int kMfmas = 1;     // kUnit / 32
+  static constexpr int kUnroll = 8;    // units per pass: weight loads in flight per wave and tile
+  static constexpr bool kCut = false;  // K % kUnit != 0 is refused
+  struct Ptrs {                        // the weight side's kernel arguments, or a lane's place in a weight row
+    const uint16_t* w;
+  };
+  using Held = bf16x8;  // what a lane holds of a unit between the load and the MFMAs
+  static __device__ __forceinline__ Ptrs at(const Ptrs& a, int64_t r, int64_t K, int64_t, int kq) {
+    return {a.w + r * K + 8 * kq};
+  }
+  // whether lane group kq has its quarter of unit s: always, K % 32 == 0 is the unit
+  static __device__ __forceinline__ bool has_block(int64_t, int, int64_t) { return true; }
+  static __device__ __forceinline__ void preset(Held&) {}  // no MFMA runs without its load
+  static __device__ __forceinline__ Held load(const Ptrs& p, int64_t s) {
+    return __builtin_bit_cast(bf16x8, __builtin_nontemporal_load(reinterpret_cast<const u16x8*>(p.w + s * kUnit)));
+  }
+  static __device__ __forceinline__ bf16x8 frag(const Held& h, int) { return h; }
+};
 
-template <int MT, int ACT>
+struct Mxfp4Mfma {
+  static constexpr int kUnit = 128;  // the four blocks of the four lane groups
+  static constexpr int kMfmas = 4;
+  static constexpr int kUnroll = DTG_MXFP4_UNROLL;
+  static constexpr bool kCut = true;  // K % 128 != 0 cuts the last unit short
+  static constexpr int kBlock = 32;   // elements of one MX block: one scale byte, one 16-B load, the K of one MFMA
+  struct Ptrs {
+    const uint8_t* wq;
+    const uint8_t* scales;
+  };
+  struct Held {
+    u32x4 v;
+    uint32_t sc;
+  };
+  static __device__ __forceinline__ Ptrs at(const Ptrs& a, int64_t r, int64_t K, int64_t blocks, int kq) {
+    return {a.wq + r * (K / 2) + (kBlock / 2) * kq, a.scales + r * blocks + kq};
+  }
+  // whether lane group kq has a block in unit s; then the unit exists
+  static __device__ __forceinline__ bool has_block(int64_t s, int kq, int64_t blocks) { return 4 * s + kq < blocks; }
+  // what a lane without a block holds: the code of +0, scale 2^0
+  static __device__ __forceinline__ void preset(Held& h) { h = {u32x4{0u, 0u, 0u, 0u}, 127u}; }
+  static __device__ __forceinline__ Held load(const Ptrs& p, int64_t s) {
+    return {__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p.wq + s * (kUnit / 2))), p.scales[4 * s]};
+  }
+  // The 8 codes of dword i (elements 2 b, 2 b + 1 in byte b, low nibble first) times the scale, as bf16.  The
+  // byte select of the conversion must be a literal.
+  static __device__ __forceinline__ bf16x8 frag(const Held& h, int i) {
+    const uint32_t d = h.v[i];
+    const float scale = __uint_as_float(h.sc << 23);
+    const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 0);
+    const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 1);
+    const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 2);
+    const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 3);
+    return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+  }
+};
+
+// W...: the element types of the format's weight-side pointers, so that every format keeps its own argument list.
+template <class Fmt, int MT, int ACT, class... W>
 __global__ __launch_bounds__(kWaves * kWave) void skinny_mfma_kernel(
-    const uint16_t* __restrict__ x, int64_t x_stride, const uint16_t* __restrict__ w,
-    const uint16_t* __restrict__ bias, uint16_t* __restrict__ y, int M, int64_t N, int64_t K) {
+    const uint16_t* __restrict__ x, int64_t x_stride, const W* __restrict__... w, const uint16_t* __restrict__ bias,
+    uint16_t* __restrict__ y, int M, int64_t N, int64_t K) {
   constexpr int NW = ACT ? 2 : 1;  // weight tiles of the workgroup: plain | gate, up
+  constexpr int kUnit = Fmt::kUnit, kUnroll = Fmt::kUnroll;
   __shared__ f32x4 part[kWaves][NW * MT][kWave];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = lane & 15, kq = lane >> 4;
   const int64_t n_out = ACT ? N / 2 : N;
   const int64_t n0 = (int64_t)blockIdx.x * kTile;
+  const int64_t blocks = K / 32;  // 32-element blocks of a row: the K of one MFMA, one MX block
 
-  // this lane's operand rows at k = 8 * kq, clamped into the matrices
+  // this lane's operand rows at its quarter of unit 0, clamped into the matrices
   const int64_t c = n0 + row < n_out ? n0 + row : n_out - 1;
-  const uint16_t* wp[NW];
+  typename Fmt::Ptrs wp[NW];
 #pragma unroll
-  for (int j = 0; j < NW; ++j) wp[j] = w + (j * n_out + c) * K + 8 * kq;
+  for (int j = 0; j < NW; ++j) wp[j] = Fmt::at({w...}, j * n_out + c, K, blocks, kq);
   const uint16_t* xp[MT];
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
     const int m = kTile * t + row;
-    xp[t] = x + (int64_t)(m < M ? m : M - 1) * x_stride + 8 * kq;
+    xp[t] = x + (int64_t)(m < M ? m : M - 1) * x_stride + kq * (kUnit / 4);
   }
 
   f32x4 acc[NW][MT];
@@ -87,39 +173,52 @@ __global__ __launch_bounds__(kWaves * kWave) void skinny_mfma_kernel(
 #pragma unroll
     for (int t = 0; t < MT; ++t) acc[j][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int64_t slabs = K / kSlab;
-  // One pass: slabs s0, s0 + kWaves, ..., s0 + (kUnroll - 1) * kWaves; FULL = all of them exist.
+  // all units, and those that K does not cut short
+  const int64_t units = Fmt::kCut ? (K + kUnit - 1) / kUnit : K / kUnit, whole = K / kUnit;
+  // One pass: units s0, s0 + kWaves, ..., s0 + (kUnroll - 1) * kWaves; FULL = all of them exist and none is cut
+  // short by K.
   auto pass = [&](int64_t s0, auto full) {
     constexpr bool FULL = decltype(full)::value;
-    bf16x8 wf[kUnroll][NW];
+    typename Fmt::Held wv[kUnroll][NW];
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
       const int64_t s = s0 + u * kWaves;
-      if (FULL || s < slabs) {
 #pragma unroll
-        for (int j = 0; j < NW; ++j) wf[u][j] = frag_nt(wp[j] + s * kSlab);
+      for (int j = 0; j < NW; ++j) Fmt::preset(wv[u][j]);
+      // where K can cut a unit short, a lane's block exists only in a unit that exists
+      if (FULL || (Fmt::kCut ? Fmt::has_block(s, kq, blocks) : s < units)) {
+#pragma unroll
+        for (int j = 0; j < NW; ++j) wv[u][j] = Fmt::load(wp[j], s);
       }
     }
-    // keep the pass's weight loads ahead of its first MFMA: left alone, the scheduler sinks them between the
-    // MFMAs to save registers and two are in flight instead of kUnroll
+    // keep the pass's weight loads ahead of its first conversion or MFMA: left alone, the scheduler sinks them
+    // between the MFMAs to save registers and two are in flight instead of kUnroll
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
       const int64_t s = s0 + u * kWaves;
-      if (FULL || s < slabs) {
+      if (FULL || s < units) {
+        const bool mine = FULL || Fmt::has_block(s, kq, blocks);
 #pragma unroll
-        for (int t = 0; t < MT; ++t) {
-          const bf16x8 xf = frag(xp[t] + s * kSlab);
+        for (int i = 0; i < Fmt::kMfmas; ++i) {
+          bf16x8 wf[NW];
 #pragma unroll
-          for (int j = 0; j < NW; ++j)
-            acc[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[u][j], xf, acc[j][t], 0, 0, 0);
+          for (int j = 0; j < NW; ++j) wf[j] = Fmt::frag(wv[u][j], i);
+#pragma unroll
+          for (int t = 0; t < MT; ++t) {
+            bf16x8 xf = __builtin_bit_cast(bf16x8, u16x8{0, 0, 0, 0, 0, 0, 0, 0});
+            if (mine) xf = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u16x8*>(xp[t] + s * kUnit + 8 * i));
+#pragma unroll
+            for (int j = 0; j < NW; ++j)
+              acc[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf, acc[j][t], 0, 0, 0);
+          }
         }
       }
     }
   };
   int64_t s0 = wave;
-  for (; s0 + (kUnroll - 1) * kWaves < slabs; s0 += kUnroll * kWaves) pass(s0, std::true_type{});
-  if (s0 < slabs) pass(s0, std::false_type{});
+  for (; s0 + (kUnroll - 1) * kWaves < whole; s0 += kUnroll * kWaves) pass(s0, std::true_type{});
+  if (s0 < units) pass(s0, std::false_type{});
 
 #pragma unroll
   for (int j = 0; j < NW; ++j)
@@ -157,66 +256,63 @@ __global__ __launch_bounds__(kWaves * kWave) void skinny_mfma_kernel(
   }
 }
 
-// The checks on the operands and the grid.
-struct MfmaPlan {
-  int64_t M, N, K;
-  const uint16_t* bias = nullptr;
-  unsigned grid;
-};
-
-MfmaPlan mfma_plan(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias, int64_t act) {
-  const char* name = "skinny_linear_mfma";
-  MfmaPlan p;
-  DTG_CHECK_CUDA_BF16(x);
-  DTG_CHECK_CUDA_BF16(w);
-  DTG_CHECK(act == 0 || act == 1, name, ": act must be 0 (none) or 1 (SwiGLU)");
-  DTG_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(0) <= kMfmaMaxM, name, ": x must be [M, K] with 1 <= M <= ",
-            kMfmaMaxM);
-  p.M = x.size(0), p.K = x.size(1);
-  DTG_CHECK(p.K % kSlab == 0, name, ": K must be a multiple of ", kSlab);
-  DTG_CHECK(x.stride(1) == 1 && x.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, name,
-            ": x must have unit inner stride and 16-B aligned rows");
-  DTG_CHECK(w.dim() == 2 && w.size(1) == p.K && w.size(0) >= 1 && w.is_contiguous() && w.device() == x.device() &&
-                reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
-            name, ": w must be a contiguous 16-B aligned [N, K] on x's device");
-  p.N = w.size(0);
-  DTG_CHECK(act == 0 || p.N % 2 == 0, name, ": the SwiGLU epilogue needs an even N (gate rows, then up rows)");
-  DTG_CHECK(p.N < (int64_t(1) << 32) && p.K < (int64_t(1) << 40), name, ": matrix too large");
-  if (bias.has_value() && bias->defined()) {
-    DTG_CHECK_CUDA_BF16(*bias);
-    DTG_CHECK(bias->dim() == 1 && bias->size(0) == p.N && bias->is_contiguous() && bias->device() == x.device(), name,
-              ": bias must be a contiguous [N]");
-    p.bias = bf16_ptr(*bias);
-  }
-  p.grid = (unsigned)(((act ? p.N / 2 : p.N) + kTile - 1) / kTile);
-  return p;
+// The shared checks with this kernel's limits: up to 64 rows, K in whole MFMAs, 16 output columns per workgroup.
+skinny::Plan mfma_plan(const char* name, const char* w_layout, int w_per_elem, const at::Tensor& x,
+                       const at::Tensor& w, const c10::optional<at::Tensor>& bias, int64_t act,
+                       const char* bias_msg = nullptr) {
+  return skinny::plan(name, w_layout, kMfmaMaxM, 32, w_per_elem, kTile, x, w, bias, act, bias_msg);
 }
 
 // Launches the instantiation for ceil(p.M / 16) M tiles: MT counts down from the largest.
-template <int ACT, int MT = kMfmaMaxM / kTile>
-void mfma_launch(const MfmaPlan& p, const at::Tensor& x, const at::Tensor& w, at::Tensor& y) {
+template <class Fmt, int ACT, int MT = kMfmaMaxM / kTile, class... W>
+void mfma_launch(const skinny::Plan& p, const at::Tensor& x, at::Tensor& y, const W*... w) {
   if constexpr (MT >= 1) {
-    if ((p.M + kTile - 1) / kTile != MT) return mfma_launch<ACT, MT - 1>(p, x, w, y);
-    skinny_mfma_kernel<MT, ACT><<<p.grid, kWaves * kWave, 0, stream()>>>(bf16_ptr(x), x.stride(0), bf16_ptr(w), p.bias,
-                                                                         bf16_mut(y), (int)p.M, p.N, p.K);
+    if ((p.M + kTile - 1) / kTile != MT) return mfma_launch<Fmt, ACT, MT - 1>(p, x, y, w...);
+    skinny_mfma_kernel<Fmt, MT, ACT, W...><<<p.grid, kWaves * kWave, 0, stream()>>>(
+        bf16_ptr(x), x.stride(0), w..., p.bias, bf16_mut(y), (int)p.M, p.N, p.K);
   }
+}
+
+template <class Fmt, class... W>
+at::Tensor mfma_run(const skinny::Plan& p, const at::Tensor& x, int64_t act, const W*... w) {
+  const c10::DeviceGuard g(x.device());
+  auto y = at::empty({p.M, act ? p.N / 2 : p.N}, x.options());
+  if (act)
+    mfma_launch<Fmt, 1>(p, x, y, w...);
+  else
+    mfma_launch<Fmt, 0>(p, x, y, w...);
+  DTG_LAUNCH_CHECK();
+  return y;
 }
 
 }  // namespace
 
 at::Tensor skinny_linear_mfma(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
                               int64_t act) {
-  const auto p = mfma_plan(x, w, bias, act);
-  const c10::DeviceGuard g(x.device());
-  auto y = at::empty({p.M, act ? p.N / 2 : p.N}, x.options());
-  if (act)
-    mfma_launch<1>(p, x, w, y);
-  else
-    mfma_launch<0>(p, x, w, y);
-  DTG_LAUNCH_CHECK();
-  return y;
+  DTG_CHECK_CUDA_BF16(x);  // ahead of w, as this operator always has
+  DTG_CHECK_CUDA_BF16(w);
+  const auto p = mfma_plan("skinny_linear_mfma", ": w must be a contiguous 16-B aligned [N, K] on x's device", 1, x, w,
+                           bias, act);
+  return mfma_run<Bf16Mfma>(p, x, act, bf16_ptr(w));
 }
 
-TORCH_LIBRARY_IMPL(dtg, CUDA, m) { m.impl("skinny_linear_mfma", &skinny_linear_mfma); }
+at::Tensor skinny_linear_mxfp4(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scales,
+                               const c10::optional<at::Tensor>& bias, int64_t act) {
+  const char* name = "skinny_linear_mxfp4";
+  DTG_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16, name, ": x must be a bf16 GPU tensor");
+  DTG_CHECK(wq.is_cuda() && wq.scalar_type() == at::kByte && scales.is_cuda() && scales.scalar_type() == at::kByte,
+            name, ": wq and scales must be uint8 GPU tensors");
+  const auto p = mfma_plan(name, ": wq must be a contiguous 16-B aligned uint8 [N, K / 2] on x's device", 2, x, wq,
+                           bias, act, ": bias must be a contiguous bf16 [N] on x's device");
+  DTG_CHECK(scales.dim() == 2 && scales.size(0) == p.N && scales.size(1) == p.K / Mxfp4Mfma::kBlock &&
+                scales.is_contiguous() && scales.device() == x.device(),
+            name, ": scales must be a contiguous uint8 [N, K / 32] on x's device");
+  return mfma_run<Mxfp4Mfma>(p, x, act, wq.data_ptr<uint8_t>(), scales.data_ptr<uint8_t>());
+}
+
+TORCH_LIBRARY_IMPL(dtg, CUDA, m) {
+  m.impl("skinny_linear_mfma", &skinny_linear_mfma);
+  m.impl("skinny_linear_mxfp4", &skinny_linear_mxfp4);
+}
 
 }  // namespace dtg

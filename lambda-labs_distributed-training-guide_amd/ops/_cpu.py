@@ -235,7 +235,7 @@ SKINNY_MAX_M = 16  # rows of x the skinny kernels are instantiated for (kSkinnyM
 SKINNY_MFMA_MAX_M = 64  # rows of x the MFMA skinny kernel takes (kMfmaMaxM)
 
 
-SKINNY_MXFP4_MAX_M = 64  # rows of x the MXFP4 skinny kernel takes (kMxMaxM)
+SKINNY_MXFP4_MAX_M = 64  # rows of x the MXFP4 skinny kernel takes (kMfmaMaxM)
 
 
 def _skinny_check(name, x, w, act, chunk, w_layout, max_m=SKINNY_MAX_M, pack=1):
@@ -305,7 +305,7 @@ def skinny_linear_fp8(x, wq, scale, bias, act=0):
 def skinny_linear_mxfp4(x, wq, scales, bias, act=0):
     """y = x @ deq(wq, scales)^T (+ bias) at 1 <= M <= 64 rows and K % 32 == 0: wq uint8 [N, K / 2] (two e2m1 codes
     per byte), scales uint8 [N, K / 32] (e8m0); an f32 matmul on the dequantised matrix, one rounding; act = 1 as
-    skinny_linear (csrc/kernels/skinny_mxfp4.hip).  Refuses what the kernel refuses."""
+    skinny_linear (csrc/kernels/skinny_mfma.hip).  Refuses what the kernel refuses."""
     from .functional import dequantize_mxfp4
 
     name = "dtg: skinny_linear_mxfp4"

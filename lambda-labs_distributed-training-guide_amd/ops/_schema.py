@@ -76,7 +76,7 @@ _DEFS = [
     # the bf16 product on the matrix pipe for 1 <= M <= 64 rows (csrc/kernels/skinny_mfma.hip): K % 32 == 0, w
     # contiguous and 16-B aligned; the same act and the same promise that a row does not depend on the others
     "skinny_linear_mfma(Tensor x, Tensor w, Tensor? bias, int act=0) -> Tensor",
-    # the same product with weight-only MXFP4 (csrc/kernels/skinny_mxfp4.hip): wq uint8 [N, K / 2], two e2m1 codes
+    # the same product with weight-only MXFP4 (csrc/kernels/skinny_mfma.hip): wq uint8 [N, K / 2], two e2m1 codes
     # per byte, element 2 j in the low nibble of byte j; scales uint8 [N, K / 32], one e8m0 byte per 32 elements of a
     # row (never 0 or 255): y = x @ deq(wq, scales)^T (+ bias), 1 <= M <= 64, K % 32 == 0
     "skinny_linear_mxfp4(Tensor x, Tensor wq, Tensor scales, Tensor? bias, int act=0) -> Tensor",

@@ -926,7 +926,7 @@ def skinny_linear_fp8(x, wq, scale, b=None, act=None):
 
 
 # --------------------------------------------------------------------------------------------
-# Weight-only MXFP4 for the decode step (csrc/kernels/skinny_mxfp4.hip)
+# Weight-only MXFP4 for the decode step (csrc/kernels/skinny_mfma.hip)
 # --------------------------------------------------------------------------------------------
 # OCP microscaling FP4 (MX v1.0): e2m1 elements (sign, two exponent bits, one mantissa bit) and one shared e8m0
 # power-of-two scale per block of 32 consecutive elements of a row: 4.25 bits per weight.
@@ -985,7 +985,7 @@ def dequantize_mxfp4(wq, scales):
 def skinny_linear_mxfp4(x, wq, scales, b=None, act=None):
     """y = x @ dequantize_mxfp4(wq, scales)^T (+ b) for 1 <= M <= 64 bf16 rows of x [M, K], K % 32 == 0:
     `ops.skinny_linear_mfma` with the weights streamed as MXFP4, 4.25 bits each, and widened in registers by
-    v_cvt_scalef32_pk_bf16_fp4 (csrc/kernels/skinny_mxfp4.hip).  `wq` / `scales` as `quantize_mxfp4_rows` returns
+    v_cvt_scalef32_pk_bf16_fp4 (csrc/kernels/skinny_mfma.hip).  `wq` / `scales` as `quantize_mxfp4_rows` returns
     them.  The same `act` (bitwise `swiglu(skinny_linear_mxfp4(x, wq, scales, b))`) and the same promise: f32
     accumulation in an order that depends on K alone, so a row's result is the same alone and inside any batch of
     up to 64 rows."""

@@ -1,4 +1,4 @@
-"""ops.skinny_linear_mxfp4 on the gfx950 kernel (csrc/kernels/skinny_mxfp4.hip) and linear="skinny-mxfp4": the operand
+"""ops.skinny_linear_mxfp4 on the gfx950 kernel (csrc/kernels/skinny_mfma.hip) and linear="skinny-mxfp4": the operand
 layout exactly, the f64 bound of _skinny_cases.reference on the dequantised weights (no outliers), row invariance and
 the SwiGLU epilogue bit for bit, unread memory, refusals, and the decode mode against its dequantised twin."""
 import copy

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """ops.skinny_linear (csrc/kernels/skinny_gemm.hip), ops.skinny_linear_fp8 (the same kernel, weight-only
 e4m3), ops.skinny_linear_mfma (csrc/kernels/skinny_mfma.hip) and ops.skinny_linear_mxfp4 (weight-only MXFP4,
-csrc/kernels/skinny_mxfp4.hip) against hipBLASLt (torch.mm / addmm, +
+csrc/kernels/skinny_mfma.hip) against hipBLASLt (torch.mm / addmm, +
 ops.swiglu for the gate_up projection) in the same process, at the decode-step projection shapes of Llama-3-8B
 (and the two narrow ones of Llama-3.2-1B and Qwen3-0.6B) and M = 1, 4, 8, 16, 32, 64 rows: time per call from
 HIP events and the rate at which the weight bytes are consumed (the FP8 arm's GB/s counts its one-byte
