@@ -66,6 +66,31 @@
 // per four MFMAs and per weight tile run on the VALU in front of the matrix pipe; at 4.25 bits per weight the
 // traffic for x is 3.8 M / 16 times the weight traffic, 15x at M = 64; a scale byte is a 1-B load per lane per
 // unit.
+//
+// W4A8 (skinny_linear_mxfp4_a8, a kernel of its own below): the same MXFP4 weights against microscaled FP8
+// activations, y = deq(xq, xs) @ deq(wq, scales)^T: xq e4m3 bytes [M, K], xs one e8m0 byte per 32 consecutive
+// elements of a row, as quantize_mxfp8_rows (below) makes them from bf16.  v_mfma_scale_f32_16x16x128_f8f6f4
+// takes both operands as they lie in memory: with cbsz = 4 (A is FP4) and blgp = 0 (B is e4m3) a lane's A operand
+// is four dwords of e2m1 codes, its B operand eight dwords of e4m3 bytes, and each comes with one e8m0 scale in
+// byte 0 of a VGPR (both opsels 0).  Lane-to-k mapping, with kq = l >> 4 and both operands' row l & 15: the scale
+// of lane l on either side is that of the k 32 kq .. 32 kq + 31 of the MFMA's 128; the FP4 operand of lane l is
+// those same 32 k, in memory order (ascending bytes, low nibble first), so on the weight side one lane is one MX
+// block.  The FP8 operand is not: its dwords 0-3 are k 16 kq .. + 15 and its dwords 4-7 k 64 + 16 kq .. + 15 (the
+// layout of two 16x16x64 steps), so a lane's 32 bytes come from the blocks kq >> 1 and 2 + (kq >> 1) of the unit
+// while its scale byte is block kq's.  The operand-layout test (tests/test_skinny_mxfp4_a8_gpu.py) is the proof: 32
+// consecutive bytes per lane fail it at every k >= 16 of a block.  So the work split, the unit of 128,
+// the weight side (Mxfp4Mfma's at / has_block / preset / load: one non-temporal 16-B load and one scale byte per lane
+// and unit) and the accumulator layout are the MXFP4 kernel's; the activation side is two 16-B loads at default
+// policy, 64 bytes apart, and one scale byte of xq row m0 + (l & 15); one scaled MFMA per unit, weight tile and M
+// tile replaces four bf16 MFMAs and 16 conversions, and no conversion touches either operand.  Where K cuts a unit
+// short, what lies past K is code 0 (+0 in both formats) with scale byte 127, on both sides: exact zeros.  FP4 x FP8
+// products times powers of two are exact in f32; the summation order of output (m, n) is: inside an MFMA the
+// hardware's, units ascending within a wave, waves ascending.  It depends on K alone, so row m of a batched call
+// equals the single-row call bit for bit, as in the other formats (and so does the quantiser: a lane's block
+// depends on no other).  Reduction and epilogue are the text of skinny_mfma_kernel's, repeated: called as one
+// device function from both kernels it changed the register allocation of the existing instantiations.
+// kUnroll = 2 (-DDTG_MXFP4_A8_UNROLL=n builds others): level with 1 and ahead of 4, and where the op wins and loses,
+// in profiles/r9/skinny_mxfp4_a8/README.md.
 #include "mlp_act.h"
 #include "skinny_common.h"
 
@@ -79,9 +104,13 @@ constexpr int kTile = 16;  // output columns of a workgroup, rows of x per MFMA
 #ifndef DTG_MXFP4_UNROLL
 #define DTG_MXFP4_UNROLL 2
 #endif
+#ifndef DTG_MXFP4_A8_UNROLL
+#define DTG_MXFP4_A8_UNROLL 2
+#endif
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 struct Bf16Mfma {
   static constexpr int kUnit = 32;     // K elements of one loop step
@@ -256,27 +285,204 @@ __global__ __launch_bounds__(kWaves * kWave) void skinny_mfma_kernel(
   }
 }
 
+// W4A8: skinny_mfma_kernel's split with the scaled MFMA (header).  The weight side is Mxfp4Mfma's.
+template <int MT, int ACT>
+__global__ __launch_bounds__(kWaves * kWave) void skinny_mxfp4_a8_kernel(
+    const uint8_t* __restrict__ xq, int64_t x_stride, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ wq,
+    const uint8_t* __restrict__ scales, const uint16_t* __restrict__ bias, uint16_t* __restrict__ y, int M, int64_t N,
+    int64_t K) {
+  using Fmt = Mxfp4Mfma;
+  constexpr int NW = ACT ? 2 : 1;
+  constexpr int kUnit = Fmt::kUnit, kBlock = Fmt::kBlock, kUnroll = DTG_MXFP4_A8_UNROLL;
+  __shared__ f32x4 part[kWaves][NW * MT][kWave];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row = lane & 15, kq = lane >> 4;
+  const int64_t n_out = ACT ? N / 2 : N;
+  const int64_t n0 = (int64_t)blockIdx.x * kTile;
+  const int64_t blocks = K / kBlock;
+
+  // this lane's operand rows at its block of unit 0, clamped into the matrices
+  const int64_t c = n0 + row < n_out ? n0 + row : n_out - 1;
+  Fmt::Ptrs wp[NW];
+#pragma unroll
+  for (int j = 0; j < NW; ++j) wp[j] = Fmt::at({wq, scales}, j * n_out + c, K, blocks, kq);
+  const uint8_t* xqp[MT];
+  const uint8_t* xsp[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    const int m = kTile * t + row;
+    const int64_t mc = m < M ? m : M - 1;
+    xqp[t] = xq + mc * x_stride + kq * (kBlock / 2);  // dwords 0-3; dwords 4-7 lie 64 bytes on
+    xsp[t] = xs + mc * blocks + kq;
+  }
+
+  f32x4 acc[NW][MT];
+#pragma unroll
+  for (int j = 0; j < NW; ++j)
+#pragma unroll
+    for (int t = 0; t < MT; ++t) acc[j][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int64_t units = (K + kUnit - 1) / kUnit, whole = K / kUnit;
+  // One pass, as in skinny_mfma_kernel: units s0, s0 + kWaves, ...; FULL = all of them exist and none is cut short.
+  auto pass = [&](int64_t s0, auto full) {
+    constexpr bool FULL = decltype(full)::value;
+    Fmt::Held wv[kUnroll][NW];
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int64_t s = s0 + u * kWaves;
+#pragma unroll
+      for (int j = 0; j < NW; ++j) Fmt::preset(wv[u][j]);
+      if (FULL || Fmt::has_block(s, kq, blocks)) {
+#pragma unroll
+        for (int j = 0; j < NW; ++j) wv[u][j] = Fmt::load(wp[j], s);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // the pass's weight loads stay ahead of its first MFMA
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int64_t s = s0 + u * kWaves;
+      if (FULL || s < units) {
+        // this lane's scale, and the two blocks its halves of the FP8 operand lie in
+        const bool mine = FULL || Fmt::has_block(s, kq, blocks);
+        const bool has_lo = FULL || Fmt::has_block(s, kq >> 1, blocks), has_hi = FULL || Fmt::has_block(s, 2 + (kq >> 1), blocks);
+        i32x8 wf[NW];  // the four dwords of codes; with cbsz = 4 the MFMA reads no more
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+          const u32x4 v = wv[u][j].v;
+          wf[j] = i32x8{(int)v[0], (int)v[1], (int)v[2], (int)v[3], 0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+          u32x4 lo = {0u, 0u, 0u, 0u}, hi = {0u, 0u, 0u, 0u};
+          uint32_t xsc = 127u;
+          if (has_lo) lo = *reinterpret_cast<const u32x4*>(xqp[t] + s * kUnit);
+          if (has_hi) hi = *reinterpret_cast<const u32x4*>(xqp[t] + s * kUnit + kUnit / 2);
+          if (mine) xsc = xsp[t][4 * s];
+          const i32x8 xf = {(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+#pragma unroll
+          for (int j = 0; j < NW; ++j)
+            acc[j][t] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[j], xf, acc[j][t], /*cbsz=*/4, /*blgp=*/0, 0,
+                                                                         (int)wv[u][j].sc, 0, (int)xsc);
+        }
+      }
+    }
+  };
+  int64_t s0 = wave;
+  for (; s0 + (kUnroll - 1) * kWaves < whole; s0 += kUnroll * kWaves) pass(s0, std::true_type{});
+  if (s0 < units) pass(s0, std::false_type{});
+
+#pragma unroll
+  for (int j = 0; j < NW; ++j)
+#pragma unroll
+    for (int t = 0; t < MT; ++t) part[wave][j * MT + t][lane] = acc[j][t];
+  __syncthreads();
+  if (wave >= MT) return;
+
+  // wave t reduces M tile t: lane l holds columns n0 + 4 * kq + r of x row 16 * t + row
+  const int t = wave;
+  f32x4 sum[NW];
+#pragma unroll
+  for (int j = 0; j < NW; ++j) {
+    sum[j] = part[0][j * MT + t][lane];
+#pragma unroll
+    for (int v = 1; v < kWaves; ++v) sum[j] += part[v][j * MT + t][lane];
+  }
+  const int m = kTile * t + row;
+  if (m >= M) return;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int64_t n = n0 + 4 * kq + r;
+    if (n >= n_out) break;
+    float a = sum[0][r], b = ACT ? sum[NW - 1][r] : 0.f;
+    if (bias != nullptr) {
+      a += bf2f(bias[n]);
+      if (ACT) b += bf2f(bias[n_out + n]);
+    }
+    if (ACT) {
+      const float in[2] = {bf2f(f2bf(a)), bf2f(f2bf(b))};
+      y[m * n_out + n] = f2bf(mlp_act::SwiGLU::fwd(in));
+    } else {
+      y[m * n_out + n] = f2bf(a);
+    }
+  }
+}
+
+// quantize_mxfp8_rows: one lane owns one block of 32 consecutive elements of a row of x (bf16): four 16-B loads,
+// the amax in the lane, the scale from amax's f32 bits as kv_append_kernel (decode_attn.hip) does it -- the power of
+// two 2^k that puts amax into (224, 448]: a significand up to 1.75 = 448 / 256 goes to [256, 448] with k = E - 135, a
+// larger one to (224, 256) with k = E - 134; k floored at -100, 0 for an all-zero block -- then x * 2^-k (exact: a bf16
+// value times a power of two), clamped to +-448 by comparisons and rounded to nearest even by v_cvt_pk_fp8_f32, which
+// that kernel's tests hold to torch's cast bit for bit, subnormal codes included: ops.quantize_fp8_rows(pow2 = True)
+// of the block.  (v_cvt_scalef32_pk_fp8_bf16 would fold the multiply and skip the widening; it has not been held
+// against the rule and is not used.)  Two 16-B stores of codes and one byte k + 127, in [27, 246].  Finite input is
+// the contract, as for the torch rule; a NaN passes the comparisons and stays a NaN code.
+constexpr int kQuantThreads = 256;
+constexpr int kMinScaleExp = -100;  // ops.FP8_MIN_SCALE_EXP
+
+__global__ __launch_bounds__(kQuantThreads) void quantize_mxfp8_rows_kernel(const uint16_t* __restrict__ x,
+                                                                           int64_t x_stride, uint8_t* __restrict__ xq,
+                                                                           uint8_t* __restrict__ xs, int64_t blocks,
+                                                                           int64_t total) {
+  const int64_t gid = (int64_t)blockIdx.x * kQuantThreads + threadIdx.x;  // block gid % blocks of row gid / blocks
+  if (gid >= total) return;
+  const uint16_t* src = x + (gid / blocks) * x_stride + (gid % blocks) * Mxfp4Mfma::kBlock;
+  float v[32];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) load8(src + 8 * i, v + 8 * i);
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
+  const uint32_t ab = __float_as_uint(amax);
+  int k = (int)(ab >> 23) - ((ab & 0x7fffffu) <= 0x600000u ? 135 : 134);
+  k = k < kMinScaleExp ? kMinScaleExp : k;
+  if (amax == 0.f) k = 0;
+  const float inv = __uint_as_float((uint32_t)(127 - k) << 23);
+  u32x4 out[2];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    float q[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float f = v[4 * i + j] * inv;
+      q[j] = f > 448.f ? 448.f : (f < -448.f ? -448.f : f);
+    }
+    int d = 0;
+    d = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], d, false);
+    d = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], d, true);
+    out[i >> 2][i & 3] = (uint32_t)d;
+  }
+  u32x4* dst = reinterpret_cast<u32x4*>(xq + gid * Mxfp4Mfma::kBlock);  // xq is contiguous: row * K + 32 * block
+  dst[0] = out[0], dst[1] = out[1];
+  xs[gid] = (uint8_t)(k + 127);
+}
+
 // The shared checks with this kernel's limits: up to 64 rows, K in whole MFMAs, 16 output columns per workgroup.
 skinny::Plan mfma_plan(const char* name, const char* w_layout, int w_per_elem, const at::Tensor& x,
                        const at::Tensor& w, const c10::optional<at::Tensor>& bias, int64_t act,
-                       const char* bias_msg = nullptr) {
-  return skinny::plan(name, w_layout, kMfmaMaxM, 32, w_per_elem, kTile, x, w, bias, act, bias_msg);
+                       const char* bias_msg = nullptr, bool x_bf16 = true) {
+  return skinny::plan(name, w_layout, kMfmaMaxM, 32, w_per_elem, kTile, x, w, bias, act, bias_msg, x_bf16);
 }
+
+struct Mxfp4A8 {};  // not a weight format of skinny_mfma_kernel: skinny_mxfp4_a8_kernel, x = xq and w... = xs, wq, scales
 
 // Launches the instantiation for ceil(p.M / 16) M tiles: MT counts down from the largest.
 template <class Fmt, int ACT, int MT = kMfmaMaxM / kTile, class... W>
 void mfma_launch(const skinny::Plan& p, const at::Tensor& x, at::Tensor& y, const W*... w) {
   if constexpr (MT >= 1) {
     if ((p.M + kTile - 1) / kTile != MT) return mfma_launch<Fmt, ACT, MT - 1>(p, x, y, w...);
-    skinny_mfma_kernel<Fmt, MT, ACT, W...><<<p.grid, kWaves * kWave, 0, stream()>>>(
-        bf16_ptr(x), x.stride(0), w..., p.bias, bf16_mut(y), (int)p.M, p.N, p.K);
+    if constexpr (std::is_same_v<Fmt, Mxfp4A8>)
+      skinny_mxfp4_a8_kernel<MT, ACT><<<p.grid, kWaves * kWave, 0, stream()>>>(
+          static_cast<const uint8_t*>(x.data_ptr()), x.stride(0), w..., p.bias, bf16_mut(y), (int)p.M, p.N, p.K);
+    else
+      skinny_mfma_kernel<Fmt, MT, ACT, W...><<<p.grid, kWaves * kWave, 0, stream()>>>(
+          bf16_ptr(x), x.stride(0), w..., p.bias, bf16_mut(y), (int)p.M, p.N, p.K);
   }
 }
 
 template <class Fmt, class... W>
 at::Tensor mfma_run(const skinny::Plan& p, const at::Tensor& x, int64_t act, const W*... w) {
   const c10::DeviceGuard g(x.device());
-  auto y = at::empty({p.M, act ? p.N / 2 : p.N}, x.options());
+  auto y = at::empty({p.M, act ? p.N / 2 : p.N}, x.options().dtype(at::kBFloat16));
   if (act)
     mfma_launch<Fmt, 1>(p, x, y, w...);
   else
@@ -310,9 +516,49 @@ at::Tensor skinny_linear_mxfp4(const at::Tensor& x, const at::Tensor& wq, const 
   return mfma_run<Mxfp4Mfma>(p, x, act, wq.data_ptr<uint8_t>(), scales.data_ptr<uint8_t>());
 }
 
+at::Tensor skinny_linear_mxfp4_a8(const at::Tensor& xq, const at::Tensor& xs, const at::Tensor& wq,
+                                  const at::Tensor& scales, const c10::optional<at::Tensor>& bias, int64_t act) {
+  const char* name = "skinny_linear_mxfp4_a8";
+  DTG_CHECK(xq.is_cuda() && xq.scalar_type() == at::kFloat8_e4m3fn && xs.is_cuda() && xs.scalar_type() == at::kByte, name,
+            ": xq must be a float8_e4m3fn and xs a uint8 GPU tensor");
+  DTG_CHECK(wq.is_cuda() && wq.scalar_type() == at::kByte && scales.is_cuda() && scales.scalar_type() == at::kByte,
+            name, ": wq and scales must be uint8 GPU tensors");
+  const auto p = mfma_plan(name, ": wq must be a contiguous 16-B aligned uint8 [N, K / 2] on xq's device", 2, xq, wq,
+                           bias, act, ": bias must be a contiguous bf16 [N] on xq's device", /*x_bf16=*/false);
+  DTG_CHECK(xs.dim() == 2 && xs.size(0) == p.M && xs.size(1) == p.K / Mxfp4Mfma::kBlock && xs.is_contiguous() &&
+                xs.device() == xq.device(),
+            name, ": xs must be a contiguous uint8 [M, K / 32] on xq's device");
+  DTG_CHECK(scales.dim() == 2 && scales.size(0) == p.N && scales.size(1) == p.K / Mxfp4Mfma::kBlock &&
+                scales.is_contiguous() && scales.device() == xq.device(),
+            name, ": scales must be a contiguous uint8 [N, K / 32] on xq's device");
+  return mfma_run<Mxfp4A8>(p, xq, act, xs.data_ptr<uint8_t>(), wq.data_ptr<uint8_t>(), scales.data_ptr<uint8_t>());
+}
+
+std::tuple<at::Tensor, at::Tensor> quantize_mxfp8_rows(const at::Tensor& x) {
+  const char* name = "quantize_mxfp8_rows";
+  DTG_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16, name, ": x must be a bf16 GPU tensor");
+  DTG_CHECK(x.dim() == 2 && x.size(1) % Mxfp4Mfma::kBlock == 0, name, ": x must be [M, K] with K a multiple of 32");
+  DTG_CHECK(x.stride(1) == 1 && x.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, name,
+            ": x must have unit inner stride and 16-B aligned rows");
+  const c10::DeviceGuard g(x.device());
+  const int64_t M = x.size(0), blocks = x.size(1) / Mxfp4Mfma::kBlock, total = M * blocks;
+  auto xq = at::empty({M, x.size(1)}, x.options().dtype(at::kFloat8_e4m3fn));
+  auto xs = at::empty({M, blocks}, x.options().dtype(at::kByte));
+  const int64_t nwg = (total + kQuantThreads - 1) / kQuantThreads;
+  DTG_CHECK(nwg < (int64_t(1) << 31), name, ": too many workgroups");
+  if (total > 0) {
+    quantize_mxfp8_rows_kernel<<<(unsigned)nwg, kQuantThreads, 0, stream()>>>(
+        bf16_ptr(x), x.stride(0), static_cast<uint8_t*>(xq.data_ptr()), xs.data_ptr<uint8_t>(), blocks, total);
+    DTG_LAUNCH_CHECK();
+  }
+  return {xq, xs};
+}
+
 TORCH_LIBRARY_IMPL(dtg, CUDA, m) {
   m.impl("skinny_linear_mfma", &skinny_linear_mfma);
   m.impl("skinny_linear_mxfp4", &skinny_linear_mxfp4);
+  m.impl("skinny_linear_mxfp4_a8", &skinny_linear_mxfp4_a8);
+  m.impl("quantize_mxfp8_rows", &quantize_mxfp8_rows);
 }
 
 }  // namespace dtg

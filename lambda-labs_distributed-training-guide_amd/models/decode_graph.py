@@ -21,7 +21,7 @@ The first `warmup` steps of a run that has no graph for its bucket yet are real 
 capture stream (lazy initialisation, allocator warm-up); the capture itself executes nothing, so the
 cache is not advanced by it.  All work runs on one dedicated stream: the graph is a plain chain of
 kernels.  With linear="skinny" (and "skinny-mfma", which takes up to 64 sequences, and
-"skinny-fp8" / "skinny-mxfp4", whose quantised weight copies are static device tensors held by this object) every kernel of the step is this project's and deterministic, and the
+"skinny-fp8" / "skinny-mxfp4" / "skinny-mxfp4-a8", whose quantised weight copies are static device tensors held by this object) every kernel of the step is this project's and deterministic, and the
 captured loop returns the ids of `generate(..., decode="eager", bucketed=True)` in the same mode bit for bit; with
 linear="blas" hipBLASLt may choose other algorithms under capture and the two agree to rounding.
 """
@@ -49,10 +49,10 @@ class GraphedDecode:
         if dev.type != "cuda":
             raise ValueError("GraphedDecode needs a GPU (HIP-graph capture)")
         self.model, self.n, self.s_max, self.linear, self.warmup = model, int(n), int(s_max), linear, int(warmup)
-        # linear="skinny-fp8" / "skinny-mxfp4": static device tensors, one slot for either format
+        # linear="skinny-fp8" / "skinny-mxfp4" / "skinny-mxfp4-a8": static device tensors, one slot for either format
         self.quant = _g._check_quant(model, linear, fp8, mxfp4, build=True)
         self.fp8 = self.quant if linear == "skinny-fp8" else None
-        self.mxfp4 = self.quant if linear == "skinny-mxfp4" else None
+        self.mxfp4 = self.quant if linear in _g.MXFP4_MODES else None
         self.cache = _g.KVCache(model.config, self.n, self.s_max, device=dev, dtype=model.embed_tokens.weight.dtype,
                                 kv_cache=kv_cache)  # "fp8": codes and scales are static device tensors too
         i64 = dict(dtype=torch.long, device=dev)

@@ -23,7 +23,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .. import ops
-from ..ops.functional import SKINNY_MAX_M, SKINNY_MFMA_MAX_M, SKINNY_MXFP4_MAX_M
+from ..ops.functional import SKINNY_MAX_M, SKINNY_MFMA_MAX_M, SKINNY_MXFP4_A8_MAX_M, SKINNY_MXFP4_MAX_M
 from .gpt2 import GPT2LMHeadModel
 from .llama import LlamaForCausalLM
 
@@ -85,7 +85,7 @@ class KVCache:
         self.max_len = 0
 
 
-LINEAR_MODES = ("blas", "skinny", "skinny-fp8", "skinny-mfma", "skinny-mxfp4")
+LINEAR_MODES = ("blas", "skinny", "skinny-fp8", "skinny-mfma", "skinny-mxfp4", "skinny-mxfp4-a8")
 KV_CACHE_MODES = ("bf16", "fp8")
 
 
@@ -96,8 +96,9 @@ def _check_kv_cache(kv_cache):
 
 def linear_max_rows(linear):
     """The rows one pass may hold with this `linear` mode: 16 for "skinny" / "skinny-fp8", 64 for "skinny-mfma" /
-    "skinny-mxfp4", None (no limit) for "blas"."""
-    return {"blas": None, "skinny-mfma": SKINNY_MFMA_MAX_M, "skinny-mxfp4": SKINNY_MXFP4_MAX_M}.get(linear, SKINNY_MAX_M)
+    "skinny-mxfp4" / "skinny-mxfp4-a8", None (no limit) for "blas"."""
+    return {"blas": None, "skinny-mfma": SKINNY_MFMA_MAX_M, "skinny-mxfp4": SKINNY_MXFP4_MAX_M,
+            "skinny-mxfp4-a8": SKINNY_MXFP4_A8_MAX_M}.get(linear, SKINNY_MAX_M)
 
 
 def _check_linear(linear, n=None):
@@ -108,7 +109,9 @@ def _check_linear(linear, n=None):
         raise ValueError(f'linear="{linear}" decodes at most {limit} sequences per step, got {n}')
 
 
-QUANT_MODES = {"skinny-fp8": ("fp8", "Fp8DecodeWeights"), "skinny-mxfp4": ("mxfp4", "Mxfp4DecodeWeights")}
+QUANT_MODES = {"skinny-fp8": ("fp8", "Fp8DecodeWeights"), "skinny-mxfp4": ("mxfp4", "Mxfp4DecodeWeights"),
+               "skinny-mxfp4-a8": ("mxfp4", "Mxfp4DecodeWeights")}  # W4A8 streams the same copies
+MXFP4_MODES = ("skinny-mxfp4", "skinny-mxfp4-a8")
 
 
 def _one_quant(fp8, mxfp4):
@@ -124,13 +127,15 @@ def _quant_kw(quant):
 
 
 def _check_quant(model, linear, fp8, mxfp4=None, build=False):
-    """The quantised weight copies of a linear="skinny-fp8" (`fp8`) or linear="skinny-mxfp4" (`mxfp4`) call: as
-    given, built when `build` allows it; None for every other mode, which takes neither argument."""
+    """The quantised weight copies of a linear="skinny-fp8" (`fp8`) or linear="skinny-mxfp4" / "skinny-mxfp4-a8"
+    (`mxfp4`, one class for both) call: as given, built when `build` allows it; None for every other mode, which
+    takes neither argument."""
     quant = _one_quant(fp8, mxfp4)
     if linear != "skinny-fp8" and fp8 is not None:
         raise ValueError(f'fp8 weights were given with linear={linear!r}; they need linear="skinny-fp8"')
-    if linear != "skinny-mxfp4" and mxfp4 is not None:
-        raise ValueError(f'mxfp4 weights were given with linear={linear!r}; they need linear="skinny-mxfp4"')
+    if linear not in MXFP4_MODES and mxfp4 is not None:
+        raise ValueError(f'mxfp4 weights were given with linear={linear!r}; they need linear="skinny-mxfp4" or '
+                         '"skinny-mxfp4-a8"')
     if linear not in QUANT_MODES:
         return None
     arg, cls = QUANT_MODES[linear]
@@ -140,7 +145,7 @@ def _check_quant(model, linear, fp8, mxfp4=None, build=False):
         from . import quantized
 
         return getattr(quantized, cls)(model)
-    if getattr(quant, "mode", linear) != linear:
+    if QUANT_MODES.get(getattr(quant, "mode", linear)) != QUANT_MODES[linear]:
         raise ValueError(f"{arg} must be a {cls} of this model, got a {type(quant).__name__}")
     quant.check(model)
     return quant
@@ -154,7 +159,8 @@ def _projections(model, linear, fp8):
     through ops.skinny_linear_mfma; linear="skinny-fp8": ops.skinny_linear_fp8 on the
     e4m3 copies `fp8` (models/quantized.py; the bf16 kernel for a head without a copy); linear="skinny-mxfp4" (at
     most 64 rows): ops.skinny_linear_mxfp4 on MXFP4 copies, which travel in the same `fp8` slot here and in the
-    functions below (only layer(i, name), head() and dequantized(name) are used).  linear="blas" with
+    functions below (only layer(i, name), head() and dequantized(name) are used); linear="skinny-mxfp4-a8": the same
+    copies through ops.skinny_linear_mxfp4_a8, which quantises its input rows to MXFP8 first.  linear="blas" with
     `fp8` is the prefill of a quantised run: hipBLASLt on the bf16 matrices the copies stand for (`fp8.dequantized`,
     made where they are used and dropped), so the keys and values the prompt leaves in the cache belong to the
     same quantised model as the decode steps that read them."""
@@ -173,8 +179,9 @@ def _projections(model, linear, fp8):
         def head(h):
             return ops.linear(h, fp8.dequantized("lm_head") if fp8_head else model.lm_head_weight())
     else:
-        bf16_linear = ops.skinny_linear_mfma if linear in ("skinny-mfma", "skinny-mxfp4") else ops.skinny_linear
-        quant_linear = ops.skinny_linear_mxfp4 if linear == "skinny-mxfp4" else ops.skinny_linear_fp8
+        bf16_linear = ops.skinny_linear_mfma if linear in ("skinny-mfma",) + MXFP4_MODES else ops.skinny_linear
+        quant_linear = {"skinny-mxfp4": ops.skinny_linear_mxfp4,
+                        "skinny-mxfp4-a8": ops.skinny_linear_mxfp4_a8}.get(linear, ops.skinny_linear_fp8)
 
         def proj(x, i, name, w, bias=None, act=None):
             if fp8 is None:
@@ -245,7 +252,8 @@ def prefill(model, prompts: Sequence[torch.Tensor], cache: KVCache, rows: Option
     `fp8` (an `Fp8DecodeWeights` of this model): the prefill of a linear="skinny-fp8" run.  The GEMMs stay
     hipBLASLt in bf16, on the matrices the e4m3 copies stand for instead of the model's own, so prompt and
     decode steps see one and the same (quantised) model.  `mxfp4` (an `Mxfp4DecodeWeights`): the same for a
-    linear="skinny-mxfp4" run; giving both is an error."""
+    linear="skinny-mxfp4" or "skinny-mxfp4-a8" run; giving both is an error.  The prompt's activations stay bf16 in
+    either: a W4A8 run shares the weights between prompt and decode steps, not the activation format."""
     _check_model(model)
     fp8 = _one_quant(fp8, mxfp4)  # from here on the one slot for either format
     if fp8 is not None:
@@ -306,7 +314,9 @@ def decode_step(model, tokens: torch.Tensor, cache: KVCache, rows: Optional[Sequ
     run in `ops.skinny_linear` (at most 16 sequences); linear="skinny-mfma": in `ops.skinny_linear_mfma` (at
     most 64); linear="skinny-fp8": in `ops.skinny_linear_fp8` on
     the e4m3 weight copies `fp8` (an `Fp8DecodeWeights` of this model, required); linear="skinny-mxfp4": in
-    `ops.skinny_linear_mxfp4` (at most 64) on the MXFP4 copies `mxfp4` (an `Mxfp4DecodeWeights`, required).  `plan_len`: the host length the attention's
+    `ops.skinny_linear_mxfp4` (at most 64) on the MXFP4 copies `mxfp4` (an `Mxfp4DecodeWeights`, required);
+    linear="skinny-mxfp4-a8": W4A8, the same copies in `ops.skinny_linear_mxfp4_a8`, which rounds every projection's
+    input rows to MXFP8 (e4m3, one power-of-two scale per 32 elements) in a launch of its own (at most 64).  `plan_len`: the host length the attention's
     launch plan is made for, cache.max_len + 1 <= plan_len <= S_max (default cache.max_len + 1, the
     tightest); a captured step is planned for its whole length bucket, and an eager step given the same
     `plan_len` runs the same launches."""
@@ -340,8 +350,9 @@ def extend_step(model, tokens: torch.Tensor, q_valid: torch.Tensor, cache: KVCac
     Built from device tensors only (`q_valid` is not read on the host).  Does NOT advance cache.lens or
     cache.max_len: the caller does, by the number of tokens it accepts; what it rejects stays past lens and is
     overwritten later.  `plan_len` as in `decode_step` (default: cache.max_len + Q, capped at S_max); it must
-    cover the largest length the pass attends.  linear="skinny" / "skinny-fp8" / "skinny-mfma" / "skinny-mxfp4" run all
-    n * Q rows in one skinny GEMM, so n * Q may not exceed the mode's row limit (`linear_max_rows`: 16, 16, 64, 64).
+    cover the largest length the pass attends.  linear="skinny" / "skinny-fp8" / "skinny-mfma" / "skinny-mxfp4" /
+    "skinny-mxfp4-a8" run all n * Q rows in one skinny GEMM, so n * Q may not exceed the mode's row limit
+    (`linear_max_rows`: 16, 16, 64, 64, 64).
     `fp8` / `mxfp4` as in `decode_step`."""
     _check_model(model)
     dev = cache.lens.device
@@ -453,7 +464,11 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     prefill stays hipBLASLt in bf16 on the dequantised matrices, so the whole call computes one quantised
     model.  `fp8` is an `Fp8DecodeWeights` of this model to reuse, None quantises the model for this call.
     linear="skinny-mxfp4": the same arrangement with MXFP4 copies (4.25 bits per weight) in `ops.skinny_linear_mxfp4`,
-    for up to 64 prompts; `mxfp4` is an `Mxfp4DecodeWeights` to reuse, None quantises for this call.  Giving both `fp8`
+    for up to 64 prompts; `mxfp4` is an `Mxfp4DecodeWeights` to reuse, None quantises for this call.
+    linear="skinny-mxfp4-a8": W4A8, the same MXFP4 copies (the same `mxfp4` argument) in `ops.skinny_linear_mxfp4_a8`,
+    whose GEMM multiplies them with MXFP8 activations on v_mfma_scale_f32_16x16x128_f8f6f4; the decode steps'
+    activations are rounded to e4m3 at every projection, the prompt's are not (the prefill is the one of
+    "skinny-mxfp4"), so prompt and decode steps share the weights but not the activation format.  Giving both `fp8`
     and `mxfp4`, or either with a mode it does not belong to, is an error.  decode="graph" (GPU only): the decode loop is captured into one HIP graph
     per length bucket (`decode_bucket`) and replayed, see models/decode_graph.py; sampling then needs
     sampler="fused", whose draw counter lives on the device.  `decode` may also be a `GraphedDecode`
@@ -466,7 +481,7 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     decoding with exact-match verification.  Every step runs the last accepted id and up to k - 1 drafted ids
     of each row through one `extend_step` and keeps the drafted ids that equal the model's own id of their
     position.  Eager only; sampling needs sampler="fused".  With linear="skinny" / "skinny-fp8" (at most
-    16 rows: prompts x k) or "skinny-mfma" (at most 64) the ids are those of the plain loop planned for the same length, bit for bit.
+    16 rows: prompts x k) or "skinny-mfma" / "skinny-mxfp4" / "skinny-mxfp4-a8" (at most 64) the ids are those of the plain loop planned for the same length, bit for bit.
 
     kv_cache="fp8": the KV cache is e4m3 with one power-of-two scale per key vector (`KVCache`), about half the
     bytes; it composes with every `linear`, `decode` and `speculate` choice, and the bitwise promises above hold
@@ -482,8 +497,9 @@ def generate(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, temper
     _one_quant(fp8, mxfp4)
     if linear != "skinny-fp8" and fp8 is not None:
         raise ValueError(f'generate: fp8 weights were given with linear={linear!r}; they need linear="skinny-fp8"')
-    if linear != "skinny-mxfp4" and mxfp4 is not None:
-        raise ValueError(f'generate: mxfp4 weights were given with linear={linear!r}; they need linear="skinny-mxfp4"')
+    if linear not in MXFP4_MODES and mxfp4 is not None:
+        raise ValueError(f'generate: mxfp4 weights were given with linear={linear!r}; they need linear="skinny-mxfp4" '
+                         'or "skinny-mxfp4-a8"')
     graphed = not isinstance(decode, str)
     if not graphed and decode not in ("eager", "graph"):
         raise ValueError(f"generate: decode must be 'eager', 'graph' or a GraphedDecode, got {decode!r}")

@@ -85,7 +85,8 @@ class Fp8DecodeWeights:
 
 class Mxfp4DecodeWeights(Fp8DecodeWeights):
     """The same matrices as MXFP4 (`ops.quantize_mxfp4_rows`): (wq uint8 [N, K / 2], scales uint8 [N, K / 32]), 4.25
-    bits per weight, streamed by `ops.skinny_linear_mxfp4` with linear="skinny-mxfp4" (up to 64 rows per step).
+    bits per weight, streamed by `ops.skinny_linear_mxfp4` with linear="skinny-mxfp4" (up to 64 rows per step) and,
+    against MXFP8 activations, by `ops.skinny_linear_mxfp4_a8` with linear="skinny-mxfp4-a8".
     The interface and the reasoning are those of `Fp8DecodeWeights`: the copies live beside the untouched model,
     `dequantized(name)` is exact in bf16, and the prefill runs hipBLASLt on it.  Every matrix needs K % 32 == 0."""
 

@@ -6,7 +6,7 @@ of those positions -- argmax, or the fused sampler's draw with the row's stream 
 in the row's output -- and accepts a drafted id if and only if it equals the id the model produced for the
 position before.  A row therefore emits the ids the plain loop would have emitted, a + 1 of them per step (a =
 the accepted drafts): not ids "distributed like" them.  With linear="skinny" / "skinny-fp8" (prompts x k <= 16 rows)
-or "skinny-mfma" / "skinny-mxfp4" (<= 64 rows, e.g. 8 prompts at k = 4) every kernel on the path computes a row's result
+or "skinny-mfma" / "skinny-mxfp4" / "skinny-mxfp4-a8" (<= 64 rows, e.g. 8 prompts at k = 4) every kernel on the path computes a row's result
 independently of the other rows of the launch (skinny GEMM, norms, RoPE, the append, the verify attention against `decode_attn`, the sampler), so the ids equal, bit for bit, those of the
 eager loop planned for the same length and run in the same `linear` mode (the modes sum in different orders and
 agree with each other only to rounding).  hipBLASLt (linear="blas"), the CPU operators and a sliding window

@@ -22,6 +22,7 @@ from .functional import (  # noqa: E402
     decode_attention,
     decode_attention_multi,
     dequantize_mxfp4,
+    dequantize_mxfp8,
     dropout_add_layer_norm,
     embedding,
     fused_linear_cross_entropy,
@@ -32,6 +33,7 @@ from .functional import (  # noqa: E402
     qk_norm_rope,
     quantize_fp8_rows,
     quantize_mxfp4_rows,
+    quantize_mxfp8_rows,
     rms_norm,
     rope,
     rope_tables,
@@ -40,6 +42,7 @@ from .functional import (  # noqa: E402
     skinny_linear_fp8,
     skinny_linear_mfma,
     skinny_linear_mxfp4,
+    skinny_linear_mxfp4_a8,
     swiglu,
     swiglu_mlp,
     vocab_parallel_fused_linear_cross_entropy,
@@ -70,4 +73,5 @@ __all__ = [
     "fa_tuning", "layer_norm", "dropout_add_layer_norm", "gelu_mlp", "qk_norm_rope", "kv_cache_append", "decode_attention",
     "sample_logits", "skinny_linear", "skinny_linear_fp8", "quantize_fp8_rows", "decode_attention_multi",
     "skinny_linear_mfma", "skinny_linear_mxfp4", "quantize_mxfp4_rows", "dequantize_mxfp4",
+    "skinny_linear_mxfp4_a8", "quantize_mxfp8_rows", "dequantize_mxfp8",
 ]

@@ -318,6 +318,54 @@ def skinny_linear_mxfp4(x, wq, scales, bias, act=0):
     return _skinny_tail(name, x.float() @ dequantize_mxfp4(wq, scales).float().t(), bias, act, x.dtype)
 
 
+def quantize_mxfp8_rows(x):
+    """ops.quantize_fp8_rows(pow2=True) of every block of 32 consecutive elements of a row of x (bf16 [M, K]); the
+    power-of-two scale as an e8m0 byte (csrc/kernels/skinny_mfma.hip).  Refuses what the kernel refuses."""
+    from .functional import quantize_fp8_rows
+
+    name = "dtg: quantize_mxfp8_rows"
+    if x.dtype != torch.bfloat16:
+        raise RuntimeError(f"{name}: x must be a bf16 tensor")
+    if x.dim() != 2 or x.shape[1] % 32:
+        raise RuntimeError(f"{name}: x must be [M, K] with K a multiple of 32")
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+        raise RuntimeError(f"{name}: x must have unit inner stride and 16-B aligned rows")
+    xq, scale = quantize_fp8_rows(x.reshape(-1, 32), pow2=True)
+    return xq.reshape(x.shape), ((scale.view(torch.int32) >> 23) & 255).to(torch.uint8).reshape(x.shape[0], -1)
+
+
+def skinny_linear_mxfp4_a8(xq, xs, wq, scales, bias, act=0):
+    """y = deq(xq, xs) @ deq(wq, scales)^T (+ bias) at 1 <= M <= 64 rows and K % 32 == 0: an f32 matmul on the two
+    dequantised matrices, one rounding; act = 1 as skinny_linear (csrc/kernels/skinny_mfma.hip).  Refuses what the
+    kernel refuses."""
+    from .functional import dequantize_mxfp4, dequantize_mxfp8
+
+    name = "dtg: skinny_linear_mxfp4_a8"
+    if xq.dtype != torch.float8_e4m3fn or xs.dtype != torch.uint8:
+        raise RuntimeError(f"{name}: xq must be a float8_e4m3fn and xs a uint8 tensor")
+    if wq.dtype != torch.uint8 or scales.dtype != torch.uint8:
+        raise RuntimeError(f"{name}: wq and scales must be uint8 tensors")
+    if act not in (0, 1):
+        raise RuntimeError(f"{name}: act must be 0 (none) or 1 (SwiGLU)")
+    if xq.dim() != 2 or not 1 <= xq.shape[0] <= SKINNY_MXFP4_MAX_M:
+        raise RuntimeError(f"{name}: x must be [M, K] with 1 <= M <= {SKINNY_MXFP4_MAX_M}")
+    M, K = xq.shape
+    if K % 32:
+        raise RuntimeError(f"{name}: K must be a multiple of 32")
+    if xq.stride(1) != 1 or xq.stride(0) % 16 or xq.data_ptr() % 16:
+        raise RuntimeError(f"{name}: x must have unit inner stride and 16-B aligned rows")
+    if wq.dim() != 2 or wq.shape[1] * 2 != K or wq.shape[0] < 1 or not wq.is_contiguous() or wq.data_ptr() % 16:
+        raise RuntimeError(f"{name}: wq must be a contiguous 16-B aligned uint8 [N, K / 2] on xq's device")
+    if act and wq.shape[0] % 2:
+        raise RuntimeError(f"{name}: the SwiGLU epilogue needs an even N (gate rows, then up rows)")
+    if xs.shape != (M, K // 32) or not xs.is_contiguous():
+        raise RuntimeError(f"{name}: xs must be a contiguous uint8 [M, K / 32] on xq's device")
+    if scales.shape != (wq.shape[0], K // 32) or not scales.is_contiguous():
+        raise RuntimeError(f"{name}: scales must be a contiguous uint8 [N, K / 32] on xq's device")
+    y = dequantize_mxfp8(xq, xs).float() @ dequantize_mxfp4(wq, scales).float().t()
+    return _skinny_tail(name, y, bias, act, torch.bfloat16)
+
+
 def swiglu_bwd(dh, gu):
     inter = gu.shape[1] // 2
     g, u, d = gu[:, :inter].float(), gu[:, inter:].float(), dh.float()
@@ -948,6 +996,6 @@ for _name, _fn in list(globals().items()):
         "flash_attn_bwd_qkv_rope", "flash_attn_tuning", "layernorm_fwd", "dropout_add_layernorm_fwd", "layernorm_bwd",
         "gelu_fwd", "gelu_bwd", "gelu_bwd_t", "qk_norm_rope_fwd_", "qk_norm_rope_bwd_", "kv_cache_append_", "decode_attn",
         "sample_logits", "skinny_linear", "skinny_linear_fp8", "decode_attn_multi", "skinny_linear_mfma",
-        "kv_cache_append_fp8_", "decode_attn_fp8", "skinny_linear_mxfp4",
+        "kv_cache_append_fp8_", "decode_attn_fp8", "skinny_linear_mxfp4", "quantize_mxfp8_rows", "skinny_linear_mxfp4_a8",
     ):
         LIB.impl(_name, _fn, "CPU")

@@ -80,6 +80,14 @@ _DEFS = [
     # per byte, element 2 j in the low nibble of byte j; scales uint8 [N, K / 32], one e8m0 byte per 32 elements of a
     # row (never 0 or 255): y = x @ deq(wq, scales)^T (+ bias), 1 <= M <= 64, K % 32 == 0
     "skinny_linear_mxfp4(Tensor x, Tensor wq, Tensor scales, Tensor? bias, int act=0) -> Tensor",
+    # activations to microscaled FP8 (MXFP8, csrc/kernels/skinny_mfma.hip): x bf16 [M, K], K % 32 == 0, unit inner
+    # stride, 16-B aligned rows -> (xq float8_e4m3fn [M, K], xs uint8 [M, K / 32]); per block of 32 consecutive
+    # elements of a row the rule of ops.quantize_fp8_rows(pow2=True), the scale stored as an e8m0 byte (never 0 or 255)
+    "quantize_mxfp8_rows(Tensor x) -> (Tensor, Tensor)",
+    # W4A8 on the scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4): y = deq(xq, xs) @ deq(wq, scales)^T (+ bias) with
+    # xq / xs as quantize_mxfp8_rows makes them (xq with unit inner stride and 16-B aligned rows) and wq / scales as
+    # skinny_linear_mxfp4 takes them; 1 <= M <= 64, K % 32 == 0, y bf16, the same act and row promise
+    "skinny_linear_mxfp4_a8(Tensor xq, Tensor xs, Tensor wq, Tensor scales, Tensor? bias, int act=0) -> Tensor",
     "swiglu_fwd(Tensor gu) -> Tensor",
     "swiglu_bwd(Tensor dh, Tensor gu) -> Tensor",
     "swiglu_bwd_t(Tensor dh, Tensor gu) -> (Tensor, Tensor, Tensor)",

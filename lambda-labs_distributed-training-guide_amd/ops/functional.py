@@ -999,6 +999,58 @@ def skinny_linear_mxfp4(x, wq, scales, b=None, act=None):
     return ops.skinny_linear_mxfp4(x, wq, scales, b, act)
 
 
+# --------------------------------------------------------------------------------------------
+# W4A8 for the decode step: MXFP4 weights x MXFP8 activations on the scaled MFMA (csrc/kernels/skinny_mfma.hip)
+# --------------------------------------------------------------------------------------------
+SKINNY_MXFP4_A8_MAX_M = 64  # rows of x the W4A8 skinny kernel takes (kMfmaMaxM)
+
+
+@torch.no_grad()
+def quantize_mxfp8_rows(x):
+    """Activation quantisation to microscaled FP8 (one kernel launch): `x` bf16 [M, K], K % 32 == 0 ->
+    (xq float8_e4m3fn [M, K], xs uint8 [M, K / 32]).  Every block of 32 consecutive elements of a row gets the
+    power-of-two scale that puts its largest magnitude into (224, 448] (1 for an all-zero block, floored at
+    2^-100), stored as an e8m0 byte (exponent + 127, never 0 or 255), and its elements become the e4m3 codes of
+    x / scale, rounded to nearest even: bit for bit `quantize_fp8_rows(x.reshape(-1, 32), pow2=True)`.  A block
+    depends on no other, so a row's result is the same alone and inside a batch."""
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or x.shape[1] % MXFP4_BLOCK:
+        raise ValueError(f"quantize_mxfp8_rows: x must be a bf16 [M, K] matrix with K % {MXFP4_BLOCK} == 0, got "
+                         f"{x.dtype} {tuple(x.shape)}")
+    return ops.quantize_mxfp8_rows(x)
+
+
+@torch.no_grad()
+def dequantize_mxfp8(xq, xs):
+    """The bf16 [M, K] matrix that (xq, xs) of `quantize_mxfp8_rows` stand for.  Exact: a 4-bit significand times
+    a power of two is a bf16 value."""
+    if (xq.dim() != 2 or xs.dim() != 2 or xq.dtype != torch.float8_e4m3fn or xs.dtype != torch.uint8
+            or xq.shape[0] != xs.shape[0] or xq.shape[1] != xs.shape[1] * MXFP4_BLOCK):
+        raise ValueError(f"dequantize_mxfp8: need xq float8_e4m3fn [M, K] and xs uint8 [M, K / 32], got {xq.dtype} "
+                         f"{tuple(xq.shape)} and {xs.dtype} {tuple(xs.shape)}")
+    scale = (xs.to(torch.int32) << 23).view(torch.float32)
+    return (xq.float().reshape(*xs.shape, MXFP4_BLOCK) * scale[..., None]).reshape(xq.shape).to(torch.bfloat16)
+
+
+@torch.no_grad()
+def skinny_linear_mxfp4_a8(x, wq, scales, b=None, act=None):
+    """W4A8: y = dequantize_mxfp8(*quantize_mxfp8_rows(x)) @ dequantize_mxfp4(wq, scales)^T (+ b) for 1 <= M <= 64
+    bf16 rows of x [M, K], K % 32 == 0, in two launches: the activation quantiser, then the GEMM on
+    v_mfma_scale_f32_16x16x128_f8f6f4, which takes the e2m1 codes, the e4m3 bytes and both block scales as they lie
+    in memory (csrc/kernels/skinny_mfma.hip).  `wq` / `scales` as `quantize_mxfp4_rows` returns them.  The same `act`
+    (bitwise `swiglu(skinny_linear_mxfp4_a8(x, wq, scales, b))`) and the same promise as `skinny_linear_mxfp4`: a
+    row's result is the same alone and inside any batch of up to 64 rows.  Unlike that operator it rounds the
+    activations to e4m3 (a 4-bit significand per element, one power-of-two scale per 32)."""
+    act, b = _skinny_args("skinny_linear_mxfp4_a8", x, wq, b, act, wname="wq", max_m=SKINNY_MXFP4_A8_MAX_M, pack=2)
+    if scales.dim() != 2 or scales.shape != (wq.shape[0], x.shape[1] // MXFP4_BLOCK):
+        raise ValueError(f"skinny_linear_mxfp4_a8: scales must be [N = {wq.shape[0]}, K / 32 = {x.shape[1] // MXFP4_BLOCK}], "
+                         f"got {tuple(scales.shape)}")
+    xq, xs = quantize_mxfp8_rows(x)
+    if x.is_cuda and not _SKINNY_FUSED:
+        xd, w = dequantize_mxfp8(xq, xs), dequantize_mxfp4(wq, scales)
+        return _skinny_composed_tail(torch.mm(xd, w.t()) if b is None else torch.addmm(b, xd, w.t()), act)
+    return ops.skinny_linear_mxfp4_a8(xq, xs, wq, scales, b, act)
+
+
 def _mlp_backward(act, x, w1, w2, a, dy, b1=None, b2=None):
     """Backward of y = act(x @ w1^T (+ b1)) @ w2^T (+ b2) from the saved pre-activation a; `act`
     names the operators {act}_fwd / _bwd / _bwd_t.  Returns dx, dw1, dw2, db1, db2.

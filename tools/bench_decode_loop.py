@@ -31,17 +31,17 @@ BATCHES = (1, 8)
 PROMPT, NEW, WARM = 16, 256, 8
 ARMS = [("blas", "eager"), ("skinny", "eager"), ("skinny-fp8", "eager"), ("blas", "graph"), ("skinny", "graph"),
         ("skinny-fp8", "graph"), ("skinny-mfma", "eager"), ("skinny-mfma", "graph"), ("skinny-mxfp4", "eager"),
-        ("skinny-mxfp4", "graph")]
+        ("skinny-mxfp4", "graph"), ("skinny-mxfp4-a8", "eager"), ("skinny-mxfp4-a8", "graph")]
 
 
 def run_arm(torch, model, prompts, linear, decode, s_max, quant=None):
     """One generate()-equivalent run; returns (tokens / s of the timed steps, capture seconds, first row's ids)."""
     from dtg.models.decode_graph import GraphedDecode
-    from dtg.models.generation import KVCache, decode_bucket, decode_step, prefill
+    from dtg.models.generation import QUANT_MODES, KVCache, decode_bucket, decode_step, prefill
 
     n = len(prompts)
-    # quantised once per model, outside every clock: {"fp8": ...} / {"mxfp4": ...} for the two quantised modes
-    quant = {k: v for k, v in (quant or {}).items() if v.mode == linear}
+    # quantised once per model, outside every clock: {"fp8": ...} / {"mxfp4": ...} for the quantised modes
+    quant = {k: v for k, v in (quant or {}).items() if k == QUANT_MODES.get(linear, (None,))[0]}
     if decode == "graph":
         # the loop of GraphedDecode.run with a clock in it: two runs on one object, the first captures
         gd = GraphedDecode(model, n, s_max, linear=linear, **quant)

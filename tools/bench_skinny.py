@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """ops.skinny_linear (csrc/kernels/skinny_gemm.hip), ops.skinny_linear_fp8 (the same kernel, weight-only
-e4m3), ops.skinny_linear_mfma (csrc/kernels/skinny_mfma.hip) and ops.skinny_linear_mxfp4 (weight-only MXFP4,
-csrc/kernels/skinny_mfma.hip) against hipBLASLt (torch.mm / addmm, +
+e4m3), ops.skinny_linear_mfma (csrc/kernels/skinny_mfma.hip), ops.skinny_linear_mxfp4 (weight-only MXFP4,
+csrc/kernels/skinny_mfma.hip) and ops.skinny_linear_mxfp4_a8 (W4A8 on the same MXFP4 buffers: the activation
+quantiser plus the GEMM, "a8", and the GEMM alone on rows quantised outside the clock, "a8 gemm") against hipBLASLt (torch.mm / addmm, +
 ops.swiglu for the gate_up projection) in the same process, at the decode-step projection shapes of Llama-3-8B
 (and the two narrow ones of Llama-3.2-1B and Qwen3-0.6B) and M = 1, 4, 8, 16, 32, 64 rows: time per call from
 HIP events and the rate at which the weight bytes are consumed (the FP8 arm's GB/s counts its one-byte
@@ -99,13 +100,23 @@ def main():
                 i[0] = (i[0] + 1) % copies4
                 return ops.skinny_linear_mxfp4(x, w4[i[0]][0], w4[i[0]][1], None, act="swiglu" if act else None)
 
+            def a8():
+                i[0] = (i[0] + 1) % copies4
+                return ops.skinny_linear_mxfp4_a8(x, w4[i[0]][0], w4[i[0]][1], None, act="swiglu" if act else None)
+
+            xq, xs = ops.quantize_mxfp8_rows(x)
+
+            def a8_gemm():
+                i[0] = (i[0] + 1) % copies4
+                return torch.ops.dtg.skinny_linear_mxfp4_a8(xq, xs, w4[i[0]][0], w4[i[0]][1], None, int(act))
+
             def blas():
                 i[0] = (i[0] + 1) % copies
                 y = torch.mm(x, ws[i[0]].t())
                 return ops.swiglu(y) if act else y
 
             res, spread = {}, {}
-            arms = (("mfma", mfma), ("mx4", mx4), ("blas", blas)) + ((("kernel", kernel), ("fp8", fp8)) if M <= FMAF_MAX_M else ())
+            arms = (("mfma", mfma), ("mx4", mx4), ("a8", a8), ("a8g", a8_gemm), ("blas", blas)) + ((("kernel", kernel), ("fp8", fp8)) if M <= FMAF_MAX_M else ())
             for which, fn in arms * 2:
                 t = time_ms(torch, fn, a.min_ms)
                 spread[which] = round(100 * abs(res.get(which, t) - t) / min(res.get(which, t), t), 1)
@@ -114,7 +125,11 @@ def main():
                  "mfma_GBps": round(wbytes / res["mfma"] / 1e6, 1), "blas_over_mfma": round(res["blas"] / res["mfma"], 2),
                  "blas_us": round(res["blas"] * 1e3, 1), "blas_GBps": round(wbytes / res["blas"] / 1e6, 1),
                  "mx4_copies": copies4, "mx4_us": round(res["mx4"] * 1e3, 1), "mx4_spread_pct": spread["mx4"],
-                 "mx4_GBps": round(mxbytes / res["mx4"] / 1e6, 1), "mfma_over_mx4": round(res["mfma"] / res["mx4"], 2)}
+                 "mx4_GBps": round(mxbytes / res["mx4"] / 1e6, 1), "mfma_over_mx4": round(res["mfma"] / res["mx4"], 2),
+                 "a8_us": round(res["a8"] * 1e3, 1), "a8_spread_pct": spread["a8"], "a8_gemm_us": round(res["a8g"] * 1e3, 1),
+                 "a8_gemm_spread_pct": spread["a8g"], "a8_gemm_GBps": round(mxbytes / res["a8g"] / 1e6, 1),
+                 "mx4_over_a8": round(res["mx4"] / res["a8"], 2), "mx4_over_a8_gemm": round(res["mx4"] / res["a8g"], 2),
+                 "mfma_over_a8": round(res["mfma"] / res["a8"], 2)}
             if M <= FMAF_MAX_M:
                 r.update({"kernel_us": round(res["kernel"] * 1e3, 1), "kernel_GBps": round(wbytes / res["kernel"] / 1e6, 1),
                           "blas_over_kernel": round(res["blas"] / res["kernel"], 2),
@@ -129,10 +144,12 @@ def main():
         torch.cuda.empty_cache()
     if a.md:
         with open(a.md, "w") as fp:
-            cols = ["mx4_us", "mfma_us", "kernel_us", "fp8_us", "blas_us", "mx4_GBps", "mfma_GBps", "kernel_GBps", "fp8_GBps",
+            cols = ["a8_us", "a8_gemm_us", "a8_spread_pct", "a8_gemm_spread_pct", "a8_gemm_GBps", "mx4_over_a8",
+                    "mx4_over_a8_gemm", "mfma_over_a8", "mx4_us", "mfma_us", "kernel_us", "fp8_us", "blas_us", "mx4_GBps", "mfma_GBps", "kernel_GBps", "fp8_GBps",
                     "blas_GBps", "mx4_spread_pct", "fp8_spread_pct", "fp8_over_mx4", "mfma_over_mx4", "blas_over_mfma",
                     "kernel_over_mfma", "blas_over_kernel", "kernel_over_fp8"]
-            fp.write("| projection | N x K | M | mxfp4 kernel µs | mfma kernel µs | fmaf kernel µs | fp8 kernel µs | hipBLASLt µs | "
+            fp.write("| projection | N x K | M | W4A8 quantiser + GEMM µs | W4A8 GEMM µs | W4A8 spread % | W4A8 GEMM spread % | "
+                     "W4A8 GEMM GB/s (mxfp4 bytes) | mxfp4 / W4A8 | mxfp4 / W4A8 GEMM | mfma / W4A8 | mxfp4 kernel µs | mfma kernel µs | fmaf kernel µs | fp8 kernel µs | hipBLASLt µs | "
                      "mxfp4 GB/s (mxfp4 bytes) | mfma GB/s (weights) | fmaf GB/s (weights) | fp8 GB/s (fp8 bytes) | "
                      "hipBLASLt GB/s | mxfp4 spread % | fp8 spread % | fp8 / mxfp4 | mfma / mxfp4 | hipBLASLt / mfma | "
                      "fmaf / mfma | hipBLASLt / fmaf | fmaf / fp8 |\n")

@@ -3,7 +3,7 @@
 kernel (ops.decode_attention_multi) against Q launches of ops.decode_attention, in one process.
 
 Loop: tokens / s of `generate` at batch 1 and 4 (--batches) on Qwen3-0.6B and a Llama-3.2-1B-shaped model (random
-init), linear = blas / skinny / skinny-fp8 / skinny-mfma / skinny-mxfp4 (a mode is left out where batch x k exceeds its row
+init), linear = blas / skinny / skinny-fp8 / skinny-mfma / skinny-mxfp4 / skinny-mxfp4-a8 (a mode is left out where batch x k exceeds its row
 limit), greedy, for the plain loop and for the speculative loop under three drafters:
   oracle  proposes the plain run's own ids: everything is accepted, the ceiling of the mode;
   wrong   proposes ids that are never right: one id per verify pass, the floor (the cost of a wasted verify);
@@ -95,11 +95,11 @@ def main():
             prompts = {"random": [torch.randint(0, cfg.vocab_size, (a.prompt_len,), generator=g) for _ in range(batch)],
                        "repeat": [piece.roll(i).repeat(4) for i in range(batch)]}
             s_max = a.prompt_len + a.new
-            for linear in ("blas", "skinny", "skinny-fp8", "skinny-mfma", "skinny-mxfp4"):
+            for linear in ("blas", "skinny", "skinny-fp8", "skinny-mfma", "skinny-mxfp4", "skinny-mxfp4-a8"):
                 if batch * a.k > (linear_max_rows(linear) or batch * a.k):
                     continue
                 kw = dict(s_max=s_max, linear=linear, fp8=fp8_w if linear == "skinny-fp8" else None,
-                          mxfp4=mx_w if linear == "skinny-mxfp4" else None)
+                          mxfp4=mx_w if linear.startswith("skinny-mxfp4") else None)
                 plain = {}
                 for which, pr in prompts.items():
                     t, ids = timed(lambda pr=pr: generate(model, pr, a.new, **kw))

@@ -61,11 +61,13 @@ def main(argv=None):
     ap.add_argument("--sampler", choices=("torch", "fused"), default="torch",
                     help="torch: the chain of torch ops, one generator for the batch; fused: one HIP launch per step "
                     "with a counter-based draw per sequence (different ids for the same seed)")
-    ap.add_argument("--linear", choices=("blas", "skinny", "skinny-fp8", "skinny-mfma", "skinny-mxfp4"), default="blas",
+    ap.add_argument("--linear", choices=("blas", "skinny", "skinny-fp8", "skinny-mfma", "skinny-mxfp4", "skinny-mxfp4-a8"),
+                    default="blas",
                     help="decode-step projections: hipBLASLt, the skinny-GEMM HIP kernel, that kernel on weight-only "
                     "FP8 (e4m3, per-row scales) copies of the matrices, quantised at start (at most 16 prompts), or the "
                     "MFMA skinny-GEMM kernel (at most 64 prompts), or that kernel's weight-only MXFP4 form (e2m1 codes, one "
-                    "e8m0 scale per 32 weights, 4.25 bits per weight; quantised at start, at most 64 prompts)")
+                    "e8m0 scale per 32 weights, 4.25 bits per weight; quantised at start, at most 64 prompts), or W4A8: the same "
+                    "MXFP4 copies against activations rounded to MXFP8 per projection, on the scaled MFMA (at most 64 prompts)")
     ap.add_argument("--kv-cache", choices=("bf16", "fp8"), default="bf16",
                     help="fp8: an e4m3 KV cache with one power-of-two scale per key vector, about half the bytes")
     ap.add_argument("--decode", choices=("eager", "graph"), default="eager",
